@@ -15,8 +15,16 @@ scaling); the only RCCL calls are the barrier and the max-over-ranks of the elap
 `--gpus N` without torchrun's WORLD_SIZE spawns the N ranks itself (before any GPU call);
 under torchrun WORLD_SIZE must equal N.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--no-cpu-baseline]
-                    [--no-secondary] [--backend nccl|gloo] [--train-envs 8192]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--envs 4096] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-secondary] [--train-envs 8192]]
+                    [--backend nccl|gloo]
+
+A plain run sets up, warms up, times the --steps ticks and prints the result line (the
+headline figure and what its one timed window gives for free).  --full adds every figure
+that takes runs of its own: the extra windows, the fan fill, env_only_single_tick, the ray
+counts, the secondaries, the CPU baseline, and at N > 1 the gradient all-reduce and the C4
+training line.  --dump-outputs DIR writes the last timed tick's observation, reward, done
+and status (what a caller of the timed launch receives for that tick) as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -29,15 +37,25 @@ PKG = os.path.join(ROOT, "rl-project-heist-architect-adversarial-reinforcement-l
 sys.path[:0] = [ROOT, PKG]
 # MIOpen's find results and compiled kernels for the full-train secondaries' convolutions
 # (miopen_cache/, recorded by a bench run on MI355X): without them a fresh box spends
-# ~2 min per precision searching solvers before the first PPO update
-for _k, _v in (("MIOPEN_USER_DB_PATH", "miopen_cache"), ("MIOPEN_CUSTOM_CACHE_DIR", "miopen_cache")):
-    os.environ.setdefault(_k, os.path.join(ROOT, _v))
+# ~2 min per precision searching solvers before the first PPO update.  MIOpen opens both
+# databases read-write and records what it finds, so the process works on a private copy:
+# the checkout may be read-only, and the tracked files stay as committed
+if "MIOPEN_USER_DB_PATH" not in os.environ and "MIOPEN_CUSTOM_CACHE_DIR" not in os.environ:
+    import atexit
+    import shutil
+    import tempfile
+    _cache = tempfile.mkdtemp(prefix="heist_miopen_")
+    atexit.register(shutil.rmtree, _cache, ignore_errors=True)
+    for _f in os.listdir(os.path.join(ROOT, "miopen_cache")):
+        shutil.copyfile(os.path.join(ROOT, "miopen_cache", _f), os.path.join(_cache, _f))
+    os.environ["MIOPEN_USER_DB_PATH"] = os.environ["MIOPEN_CUSTOM_CACHE_DIR"] = _cache
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 METRIC = "Solver env-steps/sec at 20×20, 4096 envs/GPU, 1/2/4/8 MI355X"
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+DUMP_MAX_ENVS = 8192  # --dump-outputs: envs written (4,812 bytes each at 20 x 20: 39 MB)
 
 
 def log(msg):
@@ -175,16 +193,19 @@ def measure_fan_fill(env, actions, K, bufs, reps=5):
     return max(0.0, float(np.median(fill) - np.median(plain)))
 
 
-def time_env(env, actions, warmup, steps, K, world, settle_ms=0.0, extra_windows=0):
+def time_env(env, actions, warmup, steps, K, world, settle_ms=0.0, extra_windows=0, settle_launches=0,
+             keep_last=False):
     """Time `steps` env ticks over all envs after `warmup` untimed ones: K = 1 one heist_step
     launch per tick, K > 1 heist_step_multi launches of K ticks (the last one shorter), every
     tick's observation rows going to an [K, N, 3, R, C] buffer.  HIP events bracket the
     timed launches on the stream they run on, so their span / steps is the mean tick
     duration (inter-launch gaps included); the wall clock runs between two barriers and at
-    N > 1 is the max over ranks.  K > 1: an untimed clock-settle phase of settle_ms of K-tick
-    launches precedes the window (then the fan table is refilled by the warm-up ticks, as
-    without it), and extra_windows more windows (HIP events only) give the spread
-    (time_env.windows).  Returns (elapsed_s, kernel_ms_per_tick, issue_s, launches)."""
+    N > 1 is the max over ranks.  K > 1: an untimed clock-settle phase of settle_launches K-tick
+    launches (0: as many as settle_ms takes) precedes the window (then the fan table is refilled
+    by the warm-up ticks, as without it), and extra_windows more windows (HIP events only) give
+    the spread (time_env.windows).  keep_last: time_env.last_tick holds copies of the last timed
+    tick's (observation, reward, done, status).
+    Returns (elapsed_s, kernel_ms_per_tick, issue_s, launches)."""
     dev, N = env.device, env.n_envs
     dist = torch.distributed
     stream = torch.cuda.current_stream(dev)
@@ -214,16 +235,20 @@ def time_env(env, actions, warmup, steps, K, world, settle_ms=0.0, extra_windows
             return n
     run(0, warmup)
     time_env.settle = None
-    if K > 1 and settle_ms > 0:
+    if K > 1 and (settle_ms > 0 or settle_launches > 0):
         # clock settle (untimed): K-tick launches on the same handle for settle_ms, so the
         # timed window does not start on a cold / boosting clock; then the shared fan table is
         # marked stale and the warm-up launches refill it, so the timed launches read the table
-        # at the same offsets as without the settle phase (no refill inside the window)
+        # at the same offsets as without the settle phase (no refill inside the window).
+        # Every launch advances the envs, and a count that follows the host clock differs from
+        # run to run (265 and 272 launches in two 30 ms phases of one command): settle_launches
+        # fixes the count, so the window starts from the same env states in every run
         settle = prepare(0, K)
         torch.cuda.synchronize(dev)
         ts = time.perf_counter()
         n_settle = 0
-        while (time.perf_counter() - ts) * 1e3 < settle_ms or n_settle < 8:
+        while (n_settle < settle_launches) if settle_launches > 0 else \
+                ((time.perf_counter() - ts) * 1e3 < settle_ms or n_settle < 8):
             for launch in settle:
                 launch()
             n_settle += 1
@@ -250,6 +275,13 @@ def time_env(env, actions, warmup, steps, K, world, settle_ms=0.0, extra_windows
         torch.cuda.synchronize(dev)
     elapsed = time.perf_counter() - t0
     kern_ms = e0.elapsed_time(e1) / steps
+    time_env.last_tick = None
+    if keep_last:  # the last timed tick's rows, copied before any later window overwrites the buffers
+        if K > 1:
+            kk = (steps - 1) % K  # its index in the last launch (launches start at multiples of K)
+            time_env.last_tick = tuple(b[kk].clone() for b in bufs)
+        else:
+            time_env.last_tick = (env.obs.clone(), env.reward.clone(), env.done.clone(), env.status.clone())
     windows = []
     for _ in range(extra_windows if K > 1 else 0):
         # the same window again (after the same stale-table warm-up), HIP events only: the
@@ -275,6 +307,20 @@ def time_env(env, actions, warmup, steps, K, world, settle_ms=0.0, extra_windows
     time_env.last_bufs = bufs if K > 1 else None
     time_env.per_rank = per_rank
     return elapsed, kern_ms, issue_s, launches
+
+
+def dump_outputs(directory, last_tick, suffix=""):
+    """--dump-outputs: the last timed tick's arrays as float32 .npy files ([N,3,R,C] observation,
+    [N] reward, done and status; 19.7 MB at 4096 envs of 20 x 20)."""
+    os.makedirs(directory, exist_ok=True)
+    n = int(last_tick[0].shape[0])
+    rows = None
+    if n > DUMP_MAX_ENVS:  # a fixed, seeded sample of the envs keeps the files under 64 MB in all
+        rows = np.sort(np.random.default_rng(0).choice(n, DUMP_MAX_ENVS, replace=False))
+        np.save(os.path.join(directory, "env_index" + suffix + ".npy"), rows.astype(np.float64))
+    for name, t in zip(("obs", "reward", "done", "status"), last_tick):
+        a = t.cpu().numpy()
+        np.save(os.path.join(directory, name + suffix + ".npy"), (a if rows is None else a[rows]).astype(np.float32))
 
 
 def measure_rollout(env, dev, steps=20, warmup=3, precision="bf16"):
@@ -499,14 +545,23 @@ def main():
     ap.add_argument("--budget", type=int, default=15)
     ap.add_argument("--layouts", choices=("architect", "synthetic"), default="architect",
                     help="headline layout source: the fixed Architect checkpoint (C2) or the synthetic mix")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (extra windows, fan fill, single tick, ray "
+                         "counts, secondaries, CPU baseline; at N > 1 the gradient all-reduce and C4 training)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed tick's observation, reward, done and status as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-secondary", action="store_true", help="skip the rollout / full-train numbers")
     ap.add_argument("--ticks-per-launch", type=int, default=20,
                     help="K: env ticks per heist_step_multi launch in the timed region (1: one heist_step per tick)")
     ap.add_argument("--train-envs", type=int, default=8192, help="envs per GPU of the N > 1 full-train line (C4)")
-    ap.add_argument("--settle-ms", type=float, default=30.0,
-                    help="untimed K-tick launches before the timed window (clock settle), milliseconds")
+    ap.add_argument("--settle-launches", type=int, default=272,
+                    help="untimed K-tick launches before the timed window (clock settle; 272 take ~30 ms at the "
+                         "headline's shape): a fixed count, so the window's env states repeat from run to run")
+    ap.add_argument("--settle-ms", type=float, default=None,
+                    help="settle for this many milliseconds instead (the launch count, and with it the env states "
+                         "of the window, then follow the host clock; 0: no settle phase)")
     ap.add_argument("--extra-windows", type=int, default=4,
                     help="extra timed windows after the headline one (HIP events): median / spread fields")
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl",
@@ -578,35 +633,42 @@ def main():
     actions = torch.randint(0, 5, (args.warmup + args.steps, N), device=dev, generator=gen, dtype=torch.int64)
     K = max(1, min(args.ticks_per_launch, args.steps))
     elapsed, kern_ms, issue_s, launches = time_env(env, actions, args.warmup, args.steps, K, world,
-                                                   settle_ms=args.settle_ms, extra_windows=args.extra_windows)
+                                                   settle_ms=args.settle_ms or 0.0,
+                                                   settle_launches=args.settle_launches if args.settle_ms is None
+                                                   else 0,
+                                                   extra_windows=args.extra_windows if args.full else 0,
+                                                   keep_last=args.dump_outputs is not None)
     per_rank = time_env.per_rank
     windows, settle_info = list(time_env.windows), time_env.settle
-    fan_fill_ms = 0.0
-    if K > 1 and kcfg["fan_on"]:  # the table fill the timed launches did not pay (read from an earlier fill)
-        fan_fill_ms = measure_fan_fill(env, actions, K, time_env.last_bufs)
-    # the rollout's form (the policy needs each observation before the next action): one
-    # heist_step launch per tick, timed the same way at every N (collective at N > 1)
-    e1, k1, i1, _ = time_env(env, actions, args.warmup, args.steps, 1, world) if K > 1 else (elapsed, kern_ms,
-                                                                                               issue_s, launches)
-    per_rank_1 = time_env.per_rank
-    allreduce_us = None
-    if world > 1:  # the training path's one exchange step: a flat Solver-gradient all-reduce per optimizer step
-        allreduce_us = measure_allreduce_grads(dev)
+    if args.dump_outputs is not None:
+        dump_outputs(args.dump_outputs, time_env.last_tick, "" if rank == 0 else "_rank%d" % rank)
+    if args.full:
+        fan_fill_ms = 0.0
+        if K > 1 and kcfg["fan_on"]:  # the table fill the timed launches did not pay (read from an earlier fill)
+            fan_fill_ms = measure_fan_fill(env, actions, K, time_env.last_bufs)
+        # the rollout's form (the policy needs each observation before the next action): one
+        # heist_step launch per tick, timed the same way at every N (collective at N > 1)
+        e1, k1, i1, _ = time_env(env, actions, args.warmup, args.steps, 1, world) if K > 1 else (elapsed, kern_ms,
+                                                                                                   issue_s, launches)
+        per_rank_1 = time_env.per_rank
+        allreduce_us = None
+        if world > 1:  # the training path's one exchange step: a flat Solver-gradient all-reduce per optimizer step
+            allreduce_us = measure_allreduce_grads(dev)
 
-    # ALU work figure: ray samples evaluated per env-step, counted by the
-    # kernel on extra steps after the timed region
-    cnt = torch.zeros(N, dtype=torch.int64, device=dev)
-    cnt_x = torch.zeros(N, dtype=torch.int64, device=dev)
-    env.count_samples(cnt)
-    env.count_exact_rays(cnt_x)
-    n_count = 40  # Architect cameras share their parameters, so the work per tick cycles with the headings
-    count_actions = torch.randint(0, 5, (n_count, N), device=dev, generator=gen, dtype=torch.int64)
-    for k in range(n_count):
-        env.step(count_actions[k])
-    env.count_samples(None)
-    env.count_exact_rays(None)
-    samples_per_step = float(cnt.sum().item()) / (n_count * N)
-    exact_rays_per_step = float(cnt_x.sum().item()) / (n_count * N)
+        # ALU work figure: ray samples evaluated per env-step, counted by the
+        # kernel on extra steps after the timed region
+        cnt = torch.zeros(N, dtype=torch.int64, device=dev)
+        cnt_x = torch.zeros(N, dtype=torch.int64, device=dev)
+        env.count_samples(cnt)
+        env.count_exact_rays(cnt_x)
+        n_count = 40  # Architect cameras share their parameters, so the work per tick cycles with the headings
+        count_actions = torch.randint(0, 5, (n_count, N), device=dev, generator=gen, dtype=torch.int64)
+        for k in range(n_count):
+            env.step(count_actions[k])
+        env.count_samples(None)
+        env.count_exact_rays(None)
+        samples_per_step = float(cnt.sum().item()) / (n_count * N)
+        exact_rays_per_step = float(cnt_x.sum().item()) / (n_count * N)
 
     st = env.export()  # accepted placements (set_layout's rules), not the requested lists
     ncam, ngu = float(st["n_cams"].double().mean()), float(st["n_guards"].double().mean())
@@ -615,8 +677,6 @@ def main():
     total_steps = args.steps * N * world
     value = total_steps / elapsed
     ms_per_step = elapsed / args.steps * 1e3
-    fan_ms_tick = fan_fill_ms / 1024.0  # one fill serves kFanTicks = 1,024 ticks
-    achieved_fan = b_step * N / ((kern_ms + fan_ms_tick) * 1e-3) / 1e9
     achieved_wall = b_step * N / (ms_per_step * 1e-3) / 1e9
     fan_frac = shared_fan_fraction(lb.cam_params.cpu().numpy(), lb.n_cams.cpu().numpy()) if layouts is None else \
         synthetic_fan_fraction(layouts, env, args.budget)
@@ -651,50 +711,55 @@ def main():
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS,
                          "frac_wall": achieved_wall / HBM_PEAK_GBS,
-                         "frac_with_fan_fill": achieved_fan / HBM_PEAK_GBS,
-                         "fan_fill_ms_per_fill": fan_fill_ms, "fan_fill_ms_per_tick_amortised": fan_ms_tick,
                          "shared_fan_frac": fan_frac,
                          "traffic": traffic, "traffic_source": traffic_src,
                          "kernel": multi_kernel_name(kcfg, 20, 20) if K > 1 else "heist::step_kernel",
                          "kernel_ms": kern_ms, "kernel_ms_per_launch": kern_ms * K, "launches": launches,
                          "clock_settle": settle_info,
-                         "extra_windows_kernel_ms": windows,
-                         "windows_frac": None if not windows else {
-                             "n": len(windows) + 1,
-                             "median": float(np.median([b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS
-                                                        for w in windows + [kern_ms]])),
-                             "min": min(b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS for w in windows + [kern_ms]),
-                             "max": max(b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS for w in windows + [kern_ms])},
                          "algorithmic_bytes_per_env_step": b_step,
-                         "ray_samples_per_env_step": samples_per_step,
-                         "ray_samples_per_s": samples_per_step * N / (kern_ms * 1e-3),
-                         "exact_path_rays_per_env_step": exact_rays_per_step,
                          "host_issue_us_per_step": issue_s / args.steps * 1e6,
                          "note": "achieved = algorithmic bytes per env-step (SURVEY 8d) x envs / mean tick duration "
                                  "(kernel_ms: HIP events around the timed launches); frac_wall uses ms_per_step (the "
-                                 "wall clock between the barriers), frac_with_fan_fill adds the shared fan table's "
-                                 "fill amortised over the 1,024 ticks it serves (the timed launches read a table "
-                                 "an earlier launch filled); shared_fan_frac = share of the envs with cameras whose "
-                                 "camera group the table serves; with K > 1 the per-env state stays on chip between "
-                                 "ticks, so the kernel moves fewer bytes than the formula counts (see traffic)"},
-            # the rollout cannot replay K known actions (the policy needs each
-            # observation), so its env figure -- one heist_step launch per tick -- sits beside
-            # the headline at every N
-            "env_only_single_tick": {
-                "value": args.steps * N * world / e1, "unit": "env-steps/s", "kernel_ms": k1,
-                "ms_per_step": e1 / args.steps * 1e3, "host_issue_us_per_step": i1 / args.steps * 1e6,
-                "kernel": "heist::step_kernel", "workload": "one heist_step launch per tick (the rollout's form)",
-                "roofline": {"bound": "hbm", "achieved": b_step * N / (k1 * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
-                             "unit": "GB/s", "frac": b_step * N / (k1 * 1e-3) / 1e9 / HBM_PEAK_GBS}},
-            "cpu_baseline": None,
+                                 "wall clock between the barriers), frac_with_fan_fill (--full) adds the shared fan "
+                                 "table's fill amortised over the 1,024 ticks it serves (the timed launches read a "
+                                 "table an earlier launch filled); shared_fan_frac = share of the envs with cameras "
+                                 "whose camera group the table serves; with K > 1 the per-env state stays on chip "
+                                 "between ticks, so the kernel moves fewer bytes than the formula counts (see traffic)"},
         }
+        if world > 1:  # every rank's env-only time (attribution for a 1 -> N curve)
+            line["per_rank"] = {"elapsed_s": [r[0] for r in per_rank], "kernel_ms_per_tick": [r[1] for r in per_rank]}
         log("env-only: %.1f M env-steps/s, %.2f us per tick (K=%d)" % (value / 1e6, kern_ms * 1e3, K))
+    if rank == 0 and args.full:  # the figures beside the headline, each from runs of its own
+        fan_ms_tick = fan_fill_ms / 1024.0  # one fill serves kFanTicks = 1,024 ticks
+        achieved_fan = b_step * N / ((kern_ms + fan_ms_tick) * 1e-3) / 1e9
+        line["roofline"].update({
+            "frac_with_fan_fill": achieved_fan / HBM_PEAK_GBS,
+            "fan_fill_ms_per_fill": fan_fill_ms, "fan_fill_ms_per_tick_amortised": fan_ms_tick,
+            "extra_windows_kernel_ms": windows,
+            "windows_frac": None if not windows else {
+                "n": len(windows) + 1,
+                "median": float(np.median([b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS
+                                           for w in windows + [kern_ms]])),
+                "min": min(b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS for w in windows + [kern_ms]),
+                "max": max(b_step * N / (w * 1e-3) / 1e9 / HBM_PEAK_GBS for w in windows + [kern_ms])},
+            "ray_samples_per_env_step": samples_per_step,
+            "ray_samples_per_s": samples_per_step * N / (kern_ms * 1e-3),
+            "exact_path_rays_per_env_step": exact_rays_per_step})
+        # the rollout cannot replay K known actions (the policy needs each
+        # observation), so its env figure -- one heist_step launch per tick -- sits beside
+        # the headline at every N
+        line["env_only_single_tick"] = {
+            "value": args.steps * N * world / e1, "unit": "env-steps/s", "kernel_ms": k1,
+            "ms_per_step": e1 / args.steps * 1e3, "host_issue_us_per_step": i1 / args.steps * 1e6,
+            "kernel": "heist::step_kernel", "workload": "one heist_step launch per tick (the rollout's form)",
+            "roofline": {"bound": "hbm", "achieved": b_step * N / (k1 * 1e-3) / 1e9, "peak": HBM_PEAK_GBS,
+                         "unit": "GB/s", "frac": b_step * N / (k1 * 1e-3) / 1e9 / HBM_PEAK_GBS}}
+        line["cpu_baseline"] = None
         # single-GPU figures: the secondary numbers and the CPU baseline run on rank 0 at N=1
         # only (at N>1 the other ranks would idle at the closing barrier meanwhile)
-        if world > 1:  # attribution for a 1 -> N curve: every rank's env-only time, the exchange step's cost
-            line["per_rank"] = {"elapsed_s": [r[0] for r in per_rank], "kernel_ms_per_tick": [r[1] for r in per_rank],
-                                "single_tick_elapsed_s": [r[0] for r in per_rank_1],
-                                "single_tick_kernel_ms": [r[1] for r in per_rank_1]}
+        if world > 1:  # the single-tick form per rank, the exchange step's cost
+            line["per_rank"].update({"single_tick_elapsed_s": [r[0] for r in per_rank_1],
+                                     "single_tick_kernel_ms": [r[1] for r in per_rank_1]})
             line["allreduce_grads_us_per_optimizer_step"] = allreduce_us
         if not args.no_secondary and world == 1:
             sec = {}
@@ -725,7 +790,7 @@ def main():
             line["cpu_baseline"] = cpu_baseline(layouts, cfg, args.budget, target_s=args.cpu_seconds, threads=cores)
             line["cpu_baseline_1core"] = cpu_baseline(layouts, cfg, args.budget, target_s=args.cpu_seconds / 2,
                                                       threads=1)
-    if world > 1 and not args.no_secondary:
+    if args.full and world > 1 and not args.no_secondary:
         # BASELINE config 4 at N > 1: 8192 envs/GPU, the c4 curriculum at its top (budget 40),
         # every optimizer step averaging gradients with one all-reduce (collective: all ranks)
         if rank == 0:

@@ -29,7 +29,7 @@ def _run(args, timeout):
 
 def test_bench_driver_command_line(gpu_device):
     """Few steps (the driver uses --steps 20 --warmup 5): no index past the action buffer."""
-    out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--no-secondary", "--no-cpu-baseline"], 600)
+    out = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--full", "--no-secondary", "--no-cpu-baseline"], 600)
     assert out["n_gpus"] == 1 and out["steps"] == 3 and out["warmup"] == 1
     assert out["value"] > 0 and math.isfinite(out["value"])
     rf = out["roofline"]
@@ -40,6 +40,31 @@ def test_bench_driver_command_line(gpu_device):
     assert rf["fan_fill_ms_per_fill"] >= 0 and rf["shared_fan_frac"] == 1.0  # Architect batch: one camera fan
     st = out["env_only_single_tick"]  # the rollout's one-tick-per-launch figure beside it
     assert st["value"] > 0 and st["kernel"] == "heist::step_kernel"
+
+
+def test_bench_plain_run_and_dump(gpu_device, tmp_path):
+    """A plain run carries the headline only (what --full adds is absent), and --dump-outputs
+    writes the last timed tick -- here tick 4 of 5, the second tick of the second 3-tick launch --
+    as float32 arrays of the handle's shapes."""
+    import numpy as np
+    d = str(tmp_path / "dump")
+    out = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--ticks-per-launch", "3", "--envs", "256",
+                "--dump-outputs", d], 600)
+    assert out["steps"] == 5 and out["value"] > 0 and math.isfinite(out["value"])
+    assert out["unit"] == "env-steps/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert math.isclose(out["ms_per_step"], 5 * 256 / out["value"] * 1e3 / 5, rel_tol=1e-9)
+    assert out["roofline"]["kernel_ms"] > 0 and out["roofline"]["launches"] == 2
+    for k in ("env_only_single_tick", "secondary", "cpu_baseline"):
+        assert k not in out
+    assert "frac_with_fan_fill" not in out["roofline"] and "extra_windows_kernel_ms" not in out["roofline"]
+    arrs = {n: np.load(os.path.join(d, n + ".npy")) for n in ("obs", "reward", "done", "status")}
+    assert sorted(os.listdir(d)) == ["done.npy", "obs.npy", "reward.npy", "status.npy"]
+    assert arrs["obs"].shape == (256, 3, 20, 20) and all(arrs[n].shape == (256,) for n in ("reward", "done", "status"))
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert set(np.unique(arrs["done"])) <= {0.0, 1.0}
+    assert set(np.unique(arrs["obs"][:, 1])) <= {0.0, 1.0}  # channel 1: the visibility plane
+    assert arrs["obs"][:, 0].min() >= 0.0 and arrs["obs"][:, 0].max() <= 1.0  # channel 0: cell codes / 5
+    assert (arrs["obs"][:, 2, 18, 18] == -1.0).all()  # channel 2: -1 at the vault (distance term 0)
 
 
 def test_bench_refuses_profiling_kernel(gpu_device):
@@ -53,7 +78,7 @@ def test_bench_refuses_profiling_kernel(gpu_device):
 
 def test_bench_two_ranks_gloo(gpu_device):
     out = _run(["--gpus", "2", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--envs", "512",
-                "--train-envs", "256", "--no-cpu-baseline"], 900)
+                "--train-envs", "256", "--full", "--no-cpu-baseline"], 900)
     assert out["n_gpus"] == 2 and out["config"]["backend"] == "gloo"
     assert out["value"] > 0 and math.isfinite(out["value"])
     assert len(out["per_rank"]["elapsed_s"]) == 2 and len(out["per_rank"]["single_tick_kernel_ms"]) == 2

@@ -9,9 +9,9 @@
 #   pytest            the whole -m gpu suite (one process)
 #   pytest=<args>     pytest on the given files / -k expression (quoted, one word), -m gpu
 #   smoke             __graft_entry__.smoke()
-#   bench             the driver's command: bench.py --gpus 1 --steps 20 --warmup 5
-#   bench_env         the headline only: bench.py --no-secondary --no-cpu-baseline
-#   prof              rocprofv3 kernel trace + stats of the headline (bench.py --no-secondary)
+#   bench             every figure of the bench line: bench.py --gpus 1 --steps 20 --warmup 5 --full
+#   bench_env         the headline only: bench.py (a plain run)
+#   prof              rocprofv3 kernel trace + stats of the headline (a plain bench.py run)
 #   pmc               PMC passes on the headline: FETCH_SIZE, WRITE_SIZE, SQ mix (+ summaries)
 #   pmc_c4            the same on BASELINE C4's env-only command (tools/probe_env_configs.py, c4)
 #   pmc_c5            the same on BASELINE C5's (2048 envs of 32 x 32)
@@ -36,14 +36,14 @@ run() {
   if fatal $rc; then echo "== fatal exit $rc: session stops"; exit $rc; fi
   return 0
 }
-B="bench.py --no-cpu-baseline --no-secondary"
+B="bench.py"  # a plain run: the headline's launches only
 PT="python -u -m pytest -m gpu -x -v --timeout 300 --timeout-method thread"
 for step in "$@"; do
   case "$step" in
     pytest) run pytest_gpu 1100 $PT -q tests ;;
     pytest=*) run "pytest_$(echo "${step#pytest=}" | tr -c 'A-Za-z0-9_' '_' | cut -c1-40)" 900 $PT ${step#pytest=} ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench_driver 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    bench) run bench_driver 600 python3 bench.py --gpus 1 --steps 20 --warmup 5 --full ;;
     bench_env) run bench_env 300 python3 $B --steps 20 --warmup 5 ;;
     prof) run prof 600 rocprofv3 --kernel-trace --stats -d "$OUT/prof" -o heist --output-format csv -- python3 $B --steps 300 --warmup 30 ;;
     pmc)
