@@ -149,8 +149,13 @@ int heist_step_waves(heist_t h);
  * guard_cones, multi_waves, fan_on, lean, interval_fans (the HEIST_* environment knobs as heist_create resolved them,
  * then any heist_set_* calls), step_lean (1: heist_step currently runs as a one-tick
  * heist_step_multi launch on the lean kernel; HEIST_STEP_LEAN=1 at heist_create turns it on),
- * lean_waves (waves per env of the 32 x 32 lean kernel: 2 when the batch's doubled waves fit
- * the chip, HEIST_LEAN_WAVES=1/2 forces).  probe_mode != 0 selects the profiling step kernel, whose results are
+ * lean_waves (waves per env of the lean kernel as a heist_step_multi launch would run it now:
+ * 2 for the 32 x 32 kernel when the batch's doubled waves fit the chip, HEIST_LEAN_WAVES=1/2
+ * forces; 1 with stamps armed, and 1 when the lean kernel does not serve the handle).
+ * ray_chunk, step_occ and dispatch_order always report 4, 8 and 1: their knobs (samples per
+ * ray chunk, waves per SIMD the step kernel is built for, block -> env order: heaviest raycast
+ * first) were measured, removed (profiles/r01m_*, r02bd_probe_dispatch_order.log,
+ * r05e_configs_*), and the words keep their places for the ABI.  probe_mode != 0 selects the profiling step kernel, whose results are
  * wrong by design (phases skipped). */
 int heist_get_config(heist_t h, int32_t* out, int n);
 

@@ -32,9 +32,9 @@ hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, 
                       hipStream_t st);
 int vis_gap_for(int R, int C);
 int stop_map_bytes(int R, int C);
-bool env_variant_exists(int W, int U, int O, int D);
-bool multi_variant_exists(int W, int U, int O, int D);
-bool lean_two_waves(const EnvParams& p);
+bool env_variant_exists(int W, int D);
+bool multi_variant_exists(int W, int D);
+MultiRoute multi_route(const EnvParams& p);
 hipError_t launch_cone_order(int n, int R, int C, const uint8_t* walls, const int32_t* meta, const double* params,
                              uint32_t* keys_out, hipStream_t st);
 hipError_t launch_cones(int n, int R, int C, const uint8_t* walls, const int32_t* meta, const double* params,
@@ -169,14 +169,11 @@ std::vector<double> heading_table(int R, int C) {
 }
 
 // heist_step's one-tick heist_step_multi route applies: the lean kernel (step_lean_kernel) takes
-// the launch (launch_step_multi's lean20 / lean32 test) and no instrumentation is armed (the
-// step kernel's stamp and counter layouts differ from the K-tick kernel's)
+// the launch and no stamps are armed (the step kernel's stamp layout differs from the K-tick
+// kernel's; armed counters keep the launch off the lean kernel already)
 bool lean_serves(const heist_env* h) {
-  const EnvParams& p = h->p;
-  const bool lean20 = p.multi_waves == 1 && p.R == 20 && p.C == 20 && p.vis_gap == 1024;
-  const bool lean32 = p.R == 32 && p.C == 32 && p.vis_gap == 2048;
-  return h->step_lean && p.lean && (lean20 || lean32) && p.probe_mode == 0 && !p.sample_counter &&
-         !p.redo_counter && !p.stamps && p.max_cams + p.max_guards <= heist::kMaxEmitters;
+  const heist::MultiRoute r = heist::multi_route(h->p);
+  return h->step_lean && r.kind == heist::MultiRoute::kLean && !r.stamped;
 }
 
 }  // namespace
@@ -195,7 +192,7 @@ int heist_create(int R, int C, int max_steps, int sr, int sc, int vr, int vc, co
   HEIST_REQUIRE(sr >= 0 && sr < R && sc >= 0 && sc < C && vr >= 0 && vr < R && vc >= 0 && vc < C,
                 "heist_create: start/vault outside the grid");
   HEIST_REQUIRE(n_envs >= 1, "heist_create: n_envs must be >= 1");
-  // order[] packs the env index in 24 bits (a wave priority above it, order_kernel)
+  // a bound on outside input: it keeps the kernels' 32-bit env indices and grid sizes far from overflow
   HEIST_REQUIRE(n_envs <= (1 << 24), "heist_create: n_envs must be <= 16777216");
   HEIST_REQUIRE(max_cams >= 0 && max_guards >= 0 && max_cams + max_guards <= heist::kMaxEmitters,
                 "heist_create: need max_cams + max_guards <= 64");
@@ -246,12 +243,6 @@ int heist_create(int R, int C, int max_steps, int sr, int sc, int vr, int vc, co
       n_cu = 256;
     p.step_waves = 2 * (size_t)n_envs < 32 * (size_t)n_cu ? 4 : 2;
   }
-  p.ray_chunk = 4;  // tuning knobs; a combination without a compiled variant falls back to (2, 4, 8)
-  // 8 waves per SIMD (64 VGPRs): 4096 envs are two full rounds of 8 workgroups per CU
-  // (41.4 us per step vs 46.6 at the unbounded 85 VGPRs / 5 waves, profiles/r01m_*)
-  p.step_occ = 8;
-  if (const char* u = getenv("HEIST_RAY_CHUNK")) p.ray_chunk = atoi(u);
-  if (const char* o = getenv("HEIST_STEP_OCC")) p.step_occ = atoi(o);
   if (const char* w = getenv("HEIST_STEP_WAVES")) p.step_waves = atoi(w);
   p.probe_mode = 0;
   if (const char* m = getenv("HEIST_PROBE_MODE")) p.probe_mode = atoi(m);
@@ -263,33 +254,20 @@ int heist_create(int R, int C, int max_steps, int sr, int sc, int vr, int vc, co
   p.redo_counter = nullptr;
   p.stamps = nullptr;
   p.vis_gap = heist::vis_gap_for(R, C);
-  if (!heist::env_variant_exists(p.step_waves, p.ray_chunk, p.step_occ, p.vis_gap)) {
-    p.step_waves = 2;
-    p.ray_chunk = 4;
-    p.step_occ = 8;
-    p.vis_gap = heist::vis_gap_for(R, C);
-  }
+  if (!heist::env_variant_exists(p.step_waves, p.vis_gap)) p.step_waves = 2;  // no such variant: the default waves
   // K-tick kernel: one wave per env (every role in one wave, 96 VGPRs, 5 waves per SIMD, no
   // spills) once the batch gives every SIMD 4 of them -- 4096 envs: 11.9 us per tick vs 13.1
   // at 2 waves per env (8 per SIMD, 64 VGPRs + 52 spilled), profiles/r03d_bench_w*.log --
   // else the step kernel's waves per env; HEIST_MULTI_WAVES overrides
   p.multi_waves = (size_t)n_envs >= 16 * (size_t)n_cu ? 1 : p.step_waves;
   if (const char* m = getenv("HEIST_MULTI_WAVES")) p.multi_waves = atoi(m);
+  if (!heist::multi_variant_exists(p.multi_waves, p.vis_gap)) p.multi_waves = p.step_waves;
+  p.ray_chunk = 4;  // constants: EnvParams says why the fields stay
+  p.step_occ = 8;
   p.multi_occ = p.multi_waves == 1 ? 4 : 8;
-  if (const char* m = getenv("HEIST_MULTI_OCC")) p.multi_occ = atoi(m);  // A/B: waves per SIMD it is built for
-  if (!heist::multi_variant_exists(p.multi_waves, p.ray_chunk, p.multi_occ, p.vis_gap)) {
-    p.multi_waves = p.step_waves;
-    p.multi_occ = 8;
-  }
-  // Heaviest-raycast-first dispatch (order_kernel) also pays when the whole grid is
-  // resident at once: it deals every CU one env of each cost stratum.  Block b = env b
-  // (HEIST_DISPATCH_ORDER=0, no order[] load) measured 16.29 vs 15.37 us per 4096-env step
-  // (profiles/r02bd_probe_dispatch_order.log).
   p.dispatch_order = 1;
-  if (const char* m = getenv("HEIST_DISPATCH_ORDER")) p.dispatch_order = atoi(m) >= 2 ? 2 : (atoi(m) ? 1 : 0);
-  p.n_cu = n_cu;
   p.prio_mode = 0;
-  if (const char* m = getenv("HEIST_PRIO_MODE")) p.prio_mode = atoi(m) < 0 ? 0 : (atoi(m) > 3 ? 3 : atoi(m));
+  p.n_cu = n_cu;
   p.lean_waves = 0;
   if (const char* m = getenv("HEIST_LEAN_WAVES")) p.lean_waves = atoi(m) == 1 ? 1 : (atoi(m) == 2 ? 2 : 0);
   p.split_obs = 1;
@@ -445,12 +423,11 @@ int heist_step_multi(heist_t h, int K, const int64_t* actions, float* obs_out, f
   // the shared fan table (FanTick): refilled when stale, used up, or last used by a launch on
   // another stream (streams do not order a refill against a launch still reading the table:
   // the new stream waits, on the device, for the event recorded behind the last K-tick
-  // launch), else read at the launch's offset -- only when the K-tick kernel runs (otherwise
-  // K single ticks advance the headings)
+  // launch), else read at the launch's offset -- only when a K-tick kernel that reads the table
+  // runs (otherwise K single ticks advance the headings)
   EnvParams q = h->p;
-  const bool kt = heist::multi_variant_exists(q.multi_waves, q.ray_chunk, q.multi_occ, q.vis_gap) && (q.C & 3) == 0 &&
-                  (q.probe_mode == 0 || (q.probe_mode >= 21 && q.probe_mode <= 28)) && !q.sample_counter &&
-                  !q.redo_counter;  // 21-28: the lean kernel's profiling variants (shared fan kept)
+  const heist::MultiRoute route = heist::multi_route(q);
+  const bool kt = route.kind == heist::MultiRoute::kGeneric || route.kind == heist::MultiRoute::kLean;
   q.fan_fill = 0;
   q.fan_base = 0;
   int next_pos = -1;
@@ -527,10 +504,12 @@ int heist_get_config(heist_t h, int32_t* out, int n) {
   if (int rc = check_handle(h)) return rc;
   HEIST_REQUIRE(out != nullptr && n >= 0 && n <= 16, "heist_get_config: need out != NULL and 0 <= n <= 16");
   const EnvParams& p = h->p;
-  const int32_t v[16] = {p.step_waves, p.ray_chunk,  p.step_occ,       p.vis_gap,   p.obs_store,  p.ray_mode,
+  const heist::MultiRoute r = heist::multi_route(p);
+  // ray_chunk, step_occ and dispatch_order are constants now (4, 8, 1: heaviest first): the words stay for the ABI
+  const int32_t v[16] = {p.step_waves, p.ray_chunk,      p.step_occ,  p.vis_gap,     p.obs_store,   p.ray_mode,
                          p.probe_mode, p.dispatch_order, p.split_obs, p.guard_cones, p.multi_waves, p.fan_on,
-                         p.lean,       p.interval_fans,  lean_serves(h) ? 1 : 0,
-                         p.R == 32 && p.C == 32 && heist::lean_two_waves(p) ? 2 : 1};
+                         p.lean,       p.interval_fans, lean_serves(h) ? 1 : 0,
+                         r.kind == heist::MultiRoute::kLean ? r.waves : 1};
   for (int k = 0; k < n; ++k) out[k] = v[k];
   return 0;
 }

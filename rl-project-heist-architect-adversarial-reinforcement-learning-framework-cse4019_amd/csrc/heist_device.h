@@ -135,21 +135,21 @@ struct EnvParams {
   double axis_heading[4];     // heading_tab at (dr,dc) = (-1,0), (1,0), (0,-1), (0,1)
   int step_waves;             // wavefronts per env in step/reset (1, 2 or 4)
   int multi_waves;            // wavefronts per env in the K-tick kernel (heist_step_multi; HEIST_MULTI_WAVES)
-  int multi_occ;              // min waves per SIMD it is compiled for (8 at 2 or 4 waves, 4 at 1: 128 VGPRs)
-  int ray_chunk;              // samples per ray computed together (2, 4)
-  int step_occ;               // min waves per SIMD the step kernel is compiled for (1, 8)
-  int vis_gap;                // LDS distance stop map -> vis plane (1024, 2048 or 6144), see heist_env.hip
+  int multi_occ, ray_chunk, step_occ;  // constants (heist_create): their knobs were measured, removed; no kernel
+                              // reads them, the words keep the kernel argument layout (see dispatch_order)
+  int vis_gap;               // LDS distance stop map -> vis plane (1024, 2048 or 6144), see heist_env.hip
   unsigned long long* sample_counter;  // optional [n_envs]: ray samples evaluated per env, else null
   unsigned long long* redo_counter;    // optional [n_envs]: rays re-cast on the exact fp64 path, else null
   const double* half_deg;      // [2][kHalfDegN] glibc-exact sin, cos of m/2 degrees (m = -1440 .. 1439)
   int32_t* order;              // [n_envs] env of step/reset block b: heaviest raycast first (order_kernel)
   int split_obs;               // 1 (default): step writes obs channels 0/2 before the raycast (HEIST_SPLIT_OBS)
-  int dispatch_order;          // 1 (default): step/reset block b runs env order[b] (heaviest first); 2 (opt-in,
-                               // HEIST_DISPATCH_ORDER=2, measured and not kept): the same ranks snake-drafted over
-                               // the SIMDs (order_kernel); 0: env b
-  int n_cu;                    // compute units of the device (the snake draft's SIMD count / 4)
-  int prio_mode;               // K-tick lean kernel wave priority by cost rank (order_kernel; HEIST_PRIO_MODE)
-  int lean_waves;              // 32 x 32 lean kernel waves per env: 0 auto (2 when they fit the chip), 1, 2
+  int dispatch_order;          // always 1: step/reset block b runs env order[b] (heaviest first).  Its knob and
+                               // prio_mode's were measured, removed; the kernels' tests of the two fields stay
+                               // for now: without them ROCm 7.2 clang allocates step_lean_kernel's registers
+                               // differently (C5, 32 x 32 at two waves: 7.8 -> 8.1 us per tick)
+  int n_cu;                    // compute units of the device (the 32 x 32 lean kernel's auto wave count)
+  int prio_mode;               // always 0 (no wave priority by cost rank), see dispatch_order
+  int lean_waves;             // 32 x 32 lean kernel waves per env: 0 auto (2 when they fit the chip), 1, 2
                                // (HEIST_LEAN_WAVES)
   unsigned long long* stamps;          // optional [n_envs][waves][8]: step-kernel phase stamps (s_memtime), else null
   int obs_store;              // observation stores: 0 plain, 1 write-through (sc1), 2 nt, 3 sc1 nt (HEIST_OBS_STORE)
@@ -165,6 +165,20 @@ struct EnvParams {
                               // 3 marches with a fixed direction (no sin/cos), 4 no observation write,
                               // 5 neither rays nor observation, 6 return at entry, 7 return after the
                               // raycast; results are wrong for 1-7
+};
+
+// What a heist_step_multi launch runs for a handle's current EnvParams (multi_route,
+// heist_env.hip).
+struct MultiRoute {
+  enum Kind {
+    kSingleTicks,  // K launches of the single-tick step kernel (no K-tick variant, counters armed, probe modes 5-7)
+    kGeneric,      // step_multi_kernel<multi_waves, vis_gap>
+    kProbe,        // a profiling instance of step_multi_kernel (probe modes 1-4; no shared fan)
+    kLean,         // step_lean_kernel<grid, grid>
+  } kind;
+  int grid;      // kLean: 20 or 32
+  int waves;     // waves per env of the kernel that runs (kLean: 1 or 2)
+  bool stamped;  // the stamped variant (heist_step_stamps armed)
 };
 
 // security.py:67 max(int(fov * 2), 30); capped at 32000 rays (fov 16000 deg) so the

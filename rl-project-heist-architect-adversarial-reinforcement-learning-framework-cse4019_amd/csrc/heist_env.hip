@@ -13,6 +13,10 @@
 //     [3][R][C] float32 observation (environment.py:347-374) leaves in 16-byte stores.
 // Arithmetic follows the reference's IEEE double semantics exactly: no FMA
 // contraction, half-to-even rint(), glibc-exact sin/cos (heist_trig.h).
+// Measured, removed (each with its profile where it used to be): other waves-per-SIMD budgets
+// of the K-tick and lean kernels (kStepOcc / multi_occ, step_lean_kernel), the knobs for
+// block b = env b, the snake draft and wave priority by cost rank (block_env, order_kernel),
+// the unpacked dedup flush at two waves (cast_rays), the lean kernel's probe modes 21-28.
 #include <utility>
 
 #include "heist_device.h"
@@ -20,10 +24,6 @@
 #include "heist_trig.h"
 
 #pragma clang fp contract(off)
-
-#ifndef HEIST_LEAN_OCC
-#define HEIST_LEAN_OCC 4  // step_lean_kernel's waves per SIMD the compiler budgets registers for (A/B)
-#endif
 
 namespace heist {
 
@@ -52,7 +52,11 @@ __device__ __forceinline__ double py_mod360(double x) {
 
 __host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~size_t(15); }
 
-// order[b] = env | wave priority << 24 (order_kernel); the env a step / reset block runs
+// The env a step / reset / K-tick block runs: order[b], heaviest raycast first (order_kernel).
+// Block b = env b was measured (16.29 vs 15.37 us per 4096-env step) and its knob removed
+// (profiles/r02bd_probe_dispatch_order.log): dispatch_order is always 1 and order[b] holds
+// the env alone.  The test of the field and the mask stay until step_lean_kernel's register
+// allocation can follow (EnvParams::dispatch_order).
 constexpr int32_t kOrderEnvMask = 0xFFFFFF;
 __device__ __forceinline__ int block_env(const EnvParams& p) {
   return p.dispatch_order ? (p.order[blockIdx.x] & kOrderEnvMask) : (int)blockIdx.x;
@@ -85,8 +89,13 @@ struct EnvLds {
 // Width G of the stop ring around the grid: the longest fp32 fast-path ray (range
 // kTieMaxRange = 6) ends at most G tiles from its emitter, so every one of its sample
 // addresses lies inside the padded map, stopped or not (march_fast); the exact path's
-// U-sample chunks need G >= U.  Even, so the half-to-even rounding can carry the offset.
+// kChunk-sample chunks need G >= kChunk.  Even, so the half-to-even rounding can carry the offset.
 constexpr int kRing = 6;
+
+// Samples of an exact-path ray computed together, so that their stop-map reads overlap
+// (once a template dimension of every kernel; no variant was ever built with another value).
+constexpr int kChunk = 4;
+static_assert(kRing >= kChunk, "the exact path's chunks stay inside the ring");
 
 // The padded planes hold (R + 2G) x (C + 2G) bytes; D is the compile-time distance from
 // the stop map to the visibility plane (so one address serves both), 1024 for grids up to
@@ -150,21 +159,21 @@ __device__ __forceinline__ int round_plus(double x) {
   return (int)(uint32_t)__builtin_bit_cast(uint64_t, x + kMagic);
 }
 
-// U consecutive samples of one ray: positions, U stop-map reads in flight together, then
+// kChunk consecutive samples of one ray: positions, kChunk stop-map reads in flight together, then
 // branch-free visibility stores (a masked sample writes byte 0 of the vis plane, a ring
 // byte nobody reads).  TAIL masks samples past the ray's last one (u >= left).  OWN is the
 // number of leading samples that may land on the emitter's own tile (see cast_rays).
 // Returns the index of the chunk's first sample that ends the ray (a wall or the grid
-// edge; with TAIL also sample `left`), U if none does.
+// edge; with TAIL also sample `left`), kChunk if none does.
 // KEY (heist_cone_order): instead of marking the tile, lower its u32 first-visit key
 // keys[address] to kbase + the 1-based sample index (LDS atomic min).
-template <int U, int D, bool TAIL, int OWN, bool KEY = false>
+template <int D, bool TAIL, int OWN, bool KEY = false>
 __device__ __forceinline__ int sample_chunk(unsigned char* smem, int PC, int own, double col, double row,
                                             double dxs, double dys, double kd, int left, uint32_t* keys = nullptr,
                                             uint32_t kbase = 0) {
-  int a[U], w[U];
+  int a[kChunk], w[kChunk];
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
+  for (int u = 0; u < kChunk; ++u) {
     const double ku = kd + (double)u;  // exact small integer
     const int c = round_plus<kRing>(col + dxs * ku);  // padded column c + G
     const int r = round_plus<kRing>(row + dys * ku);
@@ -172,9 +181,9 @@ __device__ __forceinline__ int sample_chunk(unsigned char* smem, int PC, int own
     w[u] = smem[a[u]];
   }
   bool stop = false;
-  int first = U;
+  int first = kChunk;
 #pragma unroll
-  for (int u = 0; u < U; ++u) {
+  for (int u = 0; u < kChunk; ++u) {
     const bool st = w[u] != 0 || (TAIL && u >= left);
     first = (!stop && st) ? u : first;
     stop |= st;
@@ -192,24 +201,24 @@ __device__ __forceinline__ int sample_chunk(unsigned char* smem, int PC, int own
 // carries the own-tile test.  Returns the ray's sample count up to and including the
 // sample that ends it (n_samp if none does): the raycast's work figure, the same on the
 // fast path.
-template <int U, int D, int OWN, bool KEY = false>
+template <int D, int OWN, bool KEY = false>
 __device__ __forceinline__ int march(unsigned char* smem, int PC, int own, double col, double row, double dxs,
                                      double dys, int n_samp, uint32_t* keys = nullptr, uint32_t kbase = 0) {
-  if (n_samp < U) {
-    const int f = sample_chunk<U, D, true, OWN, KEY>(smem, PC, own, col, row, dxs, dys, 1.0, n_samp, keys, kbase);
+  if (n_samp < kChunk) {
+    const int f = sample_chunk<D, true, OWN, KEY>(smem, PC, own, col, row, dxs, dys, 1.0, n_samp, keys, kbase);
     return f + 1 < n_samp ? f + 1 : n_samp;
   }
-  int f = sample_chunk<U, D, false, OWN, KEY>(smem, PC, own, col, row, dxs, dys, 1.0, U, keys, kbase);
-  if (f < U) return f + 1;
-  double kd = 1.0 + U;
-  int s0 = 1 + U;
-  for (; s0 + U - 1 <= n_samp; s0 += U, kd += (double)U) {
-    f = sample_chunk<U, D, false, 0, KEY>(smem, PC, own, col, row, dxs, dys, kd, U, keys, kbase);
-    if (f < U) return s0 + f;
+  int f = sample_chunk<D, false, OWN, KEY>(smem, PC, own, col, row, dxs, dys, 1.0, kChunk, keys, kbase);
+  if (f < kChunk) return f + 1;
+  double kd = 1.0 + kChunk;
+  int s0 = 1 + kChunk;
+  for (; s0 + kChunk - 1 <= n_samp; s0 += kChunk, kd += (double)kChunk) {
+    f = sample_chunk<D, false, 0, KEY>(smem, PC, own, col, row, dxs, dys, kd, kChunk, keys, kbase);
+    if (f < kChunk) return s0 + f;
   }
   if (s0 > n_samp) return n_samp;
   const int left = n_samp - s0 + 1;
-  f = sample_chunk<U, D, true, 0, KEY>(smem, PC, own, col, row, dxs, dys, kd, left, keys, kbase);
+  f = sample_chunk<D, true, 0, KEY>(smem, PC, own, col, row, dxs, dys, kd, left, keys, kbase);
   return s0 - 1 + (f + 1 < left ? f + 1 : left);
 }
 
@@ -474,7 +483,7 @@ __device__ __forceinline__ int march_fast(uint32_t PC, uint32_t own, float dxs, 
 // A ray angle that is a whole number of half degrees (guards after an axis move; the
 // reference's default cameras: heading 0, fov 60, speed 15) reads the same glibc-exact
 // sin/cos from hd (computed by heist_trig::sincos at heist_create) instead of evaluating it.
-template <int U, int D, bool KEY = false>
+template <int D, bool KEY = false>
 __device__ __forceinline__ int exact_ray(unsigned char* smem, const Emit& E, int i, int PC, int probe,
                                          const double* hd, uint32_t* keys = nullptr) {
   const double angle = E.hmh + (E.fov * (double)i) / (double)E.num_rays;  // security.py:70
@@ -497,8 +506,8 @@ __device__ __forceinline__ int exact_ray(unsigned char* smem, const Emit& E, int
   // bit for bit; dy = -sin (security.py:72-75).
   const double col = (double)E.col, row = (double)E.row;
   const uint32_t kbase = (uint32_t)i << 12;  // first-visit key: (ray, sample) in ray-major order
-  if (E.kind == 0) return march<U, D, 2, KEY>(smem, PC, own, col, row, cs * 0.5, -sn * 0.5, n_samp, keys, kbase);
-  return march<U, D, 0, KEY>(smem, PC, own, col, row, cs, -sn, n_samp, keys, kbase);
+  if (E.kind == 0) return march<D, 2, KEY>(smem, PC, own, col, row, cs * 0.5, -sn * 0.5, n_samp, keys, kbase);
+  return march<D, 0, KEY>(smem, PC, own, col, row, cs, -sn, n_samp, keys, kbase);
 }
 
 // Wave-uniform values into scalar registers (every lane holds the same copy).
@@ -540,8 +549,8 @@ __device__ __forceinline__ int emitter_of_chunk(const EnvLds& L, int n_em, int k
 // tile is never marked by its rays.
 //
 // On the exact path a sample moves at most one tile per axis from the previous one, and a
-// chunk of U samples only starts while the ray is still inside the grid, so every sample
-// lands within U <= G tiles of the grid; a fast ray stays within its range <= G of its
+// chunk of kChunk samples only starts while the ray is still inside the grid, so every sample
+// lands within kChunk <= G tiles of the grid; a fast ray stays within its range <= G of its
 // emitter (march_fast).  The G-wide ring of stop bytes makes every lookup unconditional,
 // with no clamping.  Only a camera's first two samples (dist 0.5, 1) can round back to its
 // own tile (|dx|, |dy| < 0.5 cannot both hold beyond dist 1 since dx^2 + dy^2 = 1), and a
@@ -567,14 +576,10 @@ __device__ __forceinline__ int emitter_of_chunk(const EnvLds& L, int n_em, int k
 // directions in LDS), which is marched 64 at a time (and whenever the group changes): an
 // Architect camera fan of 0.5-degree rays has about a third as many distinct sequences as
 // rays.  tb: the tie bucket tables in LDS.
-// HEIST_PACK_FLUSH (build-time A/B switch, default 1): with two or more waves per env the
-// K-tick kernel's dedup flush packs (member, direction) pairs over the lanes (13.1 vs 13.5 us
-// per 4096-env tick at 2 waves); one wave per env keeps one march per member with a
-// wave-uniform origin (11.8 vs 12.15 us packed: the per-lane origins cost it registers),
-// profiles/r03f_bench_*pack*.log.
-#ifndef HEIST_PACK_FLUSH
-#define HEIST_PACK_FLUSH 1
-#endif
+// kPackFlush: with two or more waves per env the K-tick kernel's dedup flush packs (member,
+// direction) pairs over the lanes (13.1 vs 13.5 us per 4096-env tick at 2 waves); one wave
+// per env keeps one march per member with a wave-uniform origin (11.8 vs 12.15 us packed:
+// the per-lane origins cost it registers), profiles/r03f_bench_*pack*.log.
 
 // The shared fan's emitter for one tick (FanTick header), loaded by the K-tick kernel ahead of
 // the raycast so that the per-chunk test compares registers (a global load per chunk would put
@@ -593,12 +598,10 @@ __device__ __forceinline__ FanHdr fan_hdr(const FanTick* f) {
   return h;
 }
 
-template <int NT, int U, int D, bool COUNT, bool DEDUP = false>
+template <int NT, int D, bool COUNT, bool DEDUP = false>
 __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int probe, const double* hd,
                           const TieBuckets* tb = nullptr, float2* uq = nullptr, const FanTick* fan = nullptr,
                           FanHdr fh = FanHdr{0.0, 0.0, 0, 0, -1, 0, {0.0f, 0.0f}}) {
-  static_assert(U == 2 || U == 4, "exact-path chunk");
-  static_assert(kRing >= U, "the exact path's chunks stay inside the ring");
   constexpr int W = NT / 64;
   const int n_em = uni(L.meta[0]);
   const int n_chunk = uni(L.meta[1]);
@@ -614,7 +617,7 @@ __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int pr
   // DEDUP: the unique queue of group uk (uqn entries); flush(n) marches entries 0 .. n-1
   int uqn = 0, uk = -1;
   if (DEDUP) uq += wave * 128;
-  constexpr bool kPackFlush = HEIST_PACK_FLUSH != 0 && W >= 2;
+  constexpr bool kPackFlush = W >= 2;
   // flush(cnt): the group's cnt unique directions uq[0 .. cnt) from each of its `members`
   // tiles, packed as (member, direction) pairs p = m * cnt + j over the lanes, 64 pairs per
   // march (a 2-camera group of <= 32 unique directions: one march instead of two)
@@ -783,7 +786,7 @@ __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int pr
       const int kq = v >> 16;
       for (int m = 0; m < L.em[kq].members; ++m) {
         ++n_exact;
-        n_eval += (unsigned int)exact_ray<U, D>(smem, L.em[kq + m], v & 0xffff, PC, probe, hd);
+        n_eval += (unsigned int)exact_ray<D>(smem, L.em[kq + m], v & 0xffff, PC, probe, hd);
       }
     }
   } else {
@@ -798,7 +801,7 @@ __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int pr
       if (i <= E.num_rays && near_tie(cf, sf, xr, E.kind == 0))
         for (int m = 0; m < E.members; ++m) {
           ++n_exact;
-          n_eval += (unsigned int)exact_ray<U, D>(smem, L.em[k + m], i, PC, probe, hd);
+          n_eval += (unsigned int)exact_ray<D>(smem, L.em[k + m], i, PC, probe, hd);
         }
     }
   }
@@ -812,7 +815,7 @@ __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int pr
       if (i <= E.num_rays)
         for (int m = 0; m < E.members; ++m) {
           ++n_exact;
-          n_eval += (unsigned int)exact_ray<U, D>(smem, L.em[k + m], i, PC, probe, hd);
+          n_eval += (unsigned int)exact_ray<D>(smem, L.em[k + m], i, PC, probe, hd);
         }
     }
   }
@@ -974,7 +977,7 @@ __device__ __forceinline__ uint32_t cone_vis4(const EnvLds& L, int mc, int mg, i
 // Visibility (visibility.py:31-65) once the emitter table (n_slot slots, guards from slot
 // mc on) is in LDS and vis is zeroed.  CNT: 1 ray-sample / exact-ray counting compiled in
 // (the step kernel's counting variant), 0 not, -1 chosen at run time (reset).
-template <int NT, int U, int D, int CNT = -1>
+template <int NT, int D, int CNT = -1>
 __device__ __forceinline__ void raycast_pass(const EnvParams& p, int e, unsigned char* smem, const EnvLds& L, int n_slot,
                                              int mc, int probe = 0) {
   __syncthreads();  // emitter table, stop map and cleared vis in place
@@ -985,9 +988,9 @@ __device__ __forceinline__ void raycast_pass(const EnvParams& p, int e, unsigned
   }
   if (probe != 1 && probe != 5) {
     if (CNT == 1 || (CNT < 0 && (p.sample_counter || p.redo_counter)))
-      cast_rays<NT, U, D, true>(smem, L, p.ray_mode, probe, p.half_deg);
+      cast_rays<NT, D, true>(smem, L, p.ray_mode, probe, p.half_deg);
     else
-      cast_rays<NT, U, D, false>(smem, L, p.ray_mode, probe, p.half_deg);
+      cast_rays<NT, D, false>(smem, L, p.ray_mode, probe, p.half_deg);
   }
   __syncthreads();
   if (CNT != 0 && p.sample_counter && t == 0) p.sample_counter[e] += (unsigned int)L.meta[2];
@@ -1254,6 +1257,14 @@ __device__ __forceinline__ double guard_heading_after(const EnvParams& p, int dr
 // step / reset
 // ---------------------------------------------------------------------------
 
+// Waves per SIMD the compiler budgets a kernel's registers for (amdgpu_waves_per_eu).
+// step / reset: 8 (64 VGPRs), so 4096 envs are two full rounds of 8 workgroups per CU (41.4 us
+// per step vs 46.6 at the unbounded 85 VGPRs / 5 waves, profiles/r01m_*).  The K-tick kernel:
+// 8 as well at 2 or 4 waves per env, 4 (128 VGPRs, no spills) at one wave per env; the values
+// in between were measured and removed (profiles/r03d_bench_w*.log).
+constexpr int kStepOcc = 8;
+constexpr int multi_occ(int W) { return W == 1 ? 4 : 8; }
+
 // Phase stamps (instrumentation, heist_step_stamps): lane 0 of every wave records the
 // shader clock at phase boundaries k = 0..7 into stamps[env][wave][k] (10 slots per wave).
 // Slot 8 holds HW_ID (CU / SIMD / SE of the wave) and slot 9 XCC_ID, so that clocks are
@@ -1269,8 +1280,8 @@ __device__ __forceinline__ double guard_heading_after(const EnvParams& p, int dr
 // variant that reads EnvParams::probe_mode (HEIST_PROBE_MODE: phases skipped, results
 // wrong); the product kernel is compiled with PROBE = false, where every probe test folds
 // away, and launch_step only selects the PROBE variant when probe_mode != 0.
-template <int W, int U, int O, int D, bool STAMP, bool COUNT, bool PROBE = false>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) void step_kernel(EnvParams p, const int64_t* __restrict__ actions,
+template <int W, int D, bool STAMP, bool COUNT, bool PROBE = false>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(kStepOcc))) void step_kernel(EnvParams p, const int64_t* __restrict__ actions,
                                                        float* __restrict__ obs, float* __restrict__ rew,
                                                        double* __restrict__ rew64, uint8_t* __restrict__ done_out,
                                                        int8_t* __restrict__ status_out, int auto_reset) {
@@ -1380,7 +1391,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) voi
   if (probe == 9) return;  // profiling: everything before the raycast barrier
   HEIST_STEP_STAMP(2);
   // 3. visibility (environment.py:257-258); an already-done env recomputes the same plane
-  raycast_pass<NT, U, D, COUNT ? 1 : 0>(p, e, smem, L, n_slot, mc, probe);
+  raycast_pass<NT, D, COUNT ? 1 : 0>(p, e, smem, L, n_slot, mc, probe);
   if (probe == 7) return;  // profiling: everything up to the raycast
   HEIST_STEP_STAMP(3);
 
@@ -1467,7 +1478,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) voi
       }
       publish_emitters(L, E2, n_slot);
       clear_vis<NT>(p, L);
-      raycast_pass<NT, U, D, COUNT ? 1 : 0>(p, e, smem, L, n_slot, mc, probe);
+      raycast_pass<NT, D, COUNT ? 1 : 0>(p, e, smem, L, n_slot, mc, probe);
     } else if (moved & 2) {
       cset = 1;
     }
@@ -1817,7 +1828,7 @@ __device__ __forceinline__ void stamp_guard_cones(const EnvLds& L, uint8_t* gvis
 // PROBE (profiling variant, HEIST_PROBE_MODE at heist_create; results wrong on purpose):
 // bit 0 skips the raycast and the cone stamps, bit 1 the observation stores, bit 2 the
 // rays' marches (directions and tie screens only).
-template <int W, int U, int O, int D, bool STAMP = false, int PROBE = 0>
+template <int W, int D, bool STAMP = false, int PROBE = 0>
 __device__ __forceinline__ void step_multi_body(
     const EnvParams& p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset,
@@ -2015,7 +2026,7 @@ __device__ __forceinline__ void step_multi_body(
     // 3. visibility (environment.py:257-258)
     if (live_guard && E.kind == 1) L.vis[L.at(E.row, E.col)] = 1;  // visibility.py:59
     if (!(PROBE & 1))
-      cast_rays<NT, U, D, false, true>(smem, L, p.ray_mode, (PROBE & 4) ? 2 : 0, p.half_deg, tb, uq,
+      cast_rays<NT, D, false, true>(smem, L, p.ray_mode, (PROBE & 4) ? 2 : 0, p.half_deg, tb, uq,
                                        p.fan + p.fan_base + k, fhdr);
     if (SOLO && cached && !reset_pass) take_entry();  // loaded a tick ago; the raycast covered its latency
     if (!(PROBE & 1)) stamp_guard_cones<NT>(L, gvis, mc, mg, 0);
@@ -2136,13 +2147,13 @@ __device__ __forceinline__ void step_multi_body(
   }
 }
 
-template <int W, int U, int O, int D, bool STAMP = false, int PROBE = 0>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) void step_multi_kernel(
+template <int W, int D, bool STAMP = false, int PROBE = 0>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(multi_occ(W)))) void step_multi_kernel(
     EnvParams p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = block_env(p);
-  step_multi_body<W, U, O, D, STAMP, PROBE>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
+  step_multi_body<W, D, STAMP, PROBE>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
 }
 
 // ---------------------------------------------------------------------------
@@ -2210,7 +2221,7 @@ __device__ __noinline__ void lean_tie_rays(unsigned char* smem, const FanTick* f
       E.first = 0;
       E.kind = 0;
       E.members = 1;
-      if (tr >= 0) exact_ray<4, D>(smem, E, tr, PC, 0, hd);
+      if (tr >= 0) exact_ray<D>(smem, E, tr, PC, 0, hd);
     }
   }
 }
@@ -2232,7 +2243,7 @@ __device__ __noinline__ void ivl_tie_rays(unsigned char* smem, int ray, double h
   E.first = 0;
   E.kind = 0;
   E.members = 1;
-  if (ray >= 0) exact_ray<4, D>(smem, E, ray, PC, 0, hd);
+  if (ray >= 0) exact_ray<D>(smem, E, ray, PC, 0, hd);
 }
 
 // The lean kernel's LDS: the three padded planes (stop map, visibility, sink; the step
@@ -2348,20 +2359,19 @@ __device__ __attribute__((noinline)) void lean_generic_body(EnvParams p, int K, 
                                                             double* __restrict__ rew64, uint8_t* __restrict__ done_out,
                                                             int8_t* __restrict__ status_out, int auto_reset,
                                                             unsigned char* smem, int e) {
-  step_multi_body<1, 4, 4, D, false, 0>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
+  step_multi_body<1, D, false, 0>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
 }
 
 // STAMP (instrumentation, heist_step_stamps armed): lane 0 sums the shader clock spent in 9
 // tick segments over the launch (LEAN_SEGS in tools/probe_lean_stamps.py) in LDS after the
 // carve and writes [segment sums 0..8, lifetime, start clock, HW_ID, XCC_ID] to
 // stamps[env][0][16] (the generic K-tick body's layout); envs on the generic body record none.
-// PROBE (profiling only, HEIST_PROBE_MODE with a library built -DHEIST_LEAN_PROBES,
-// tools/build_variant.sh; results wrong): 21 no wait for the previous tick's
-// DMA, 22 no visibility cast, 23 no observation stores, 24 / 25 shared-fan marches without
-// their visibility stores / stop-byte loads, 26 the observation stores without their LDS reads,
-// 27 the stores alone (no move, cast, detection), 28 move + patrol + stores.
-template <int R_, int C_, bool STAMP = false, int PROBE = 0, int NW = 1>
-__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_LEAN_OCC))) void step_lean_kernel(
+// Registers are budgeted for 4 waves per SIMD (amdgpu_waves_per_eu): 5 was measured (61 VGPRs
+// spilled instead of 23, slower everywhere) and removed (DESIGN.md §10 item 4,
+// profiles/r06zc_occ5_env_configs.log).  The kernel's profiling instances (probe modes 21-28,
+// the removal ladder of DESIGN.md §6.3) were measured and removed too (profiles/r05t_lean_ab.log).
+template <int R_, int C_, bool STAMP = false, int NW = 1>
+__global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void step_lean_kernel(
     EnvParams p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset) {
   constexpr int D = lean_gap(R_, C_);
@@ -2373,12 +2383,12 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
   constexpr int OFF0 = kRing * PC + kRing;  // padded index of tile (0, 0); also a sample's offset on its own tile
   static_assert((R_ + 2 * kRing) * PC <= D, "the padded planes fit the 1024-byte gap");
   static_assert(C_ % 4 == 0 && R_ <= 64 && C_ <= 32 && (R_ + 2 * kRing) * PC <= 2048, "lean kernel geometry");
-  static_assert(NW == 1 || (NW == 2 && !STAMP && PROBE == 0 && Q % 2 == 0), "two waves: the plain form, even Q");
+  static_assert(NW == 1 || (NW == 2 && !STAMP && Q % 2 == 0), "two waves: the plain form, even Q");
   constexpr int QW = Q / NW;          // observation quads per lane this wave stores
   constexpr int kStores = 3 * QW + 4;  // a wave's stores per tick (see 6. below)
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = block_env(p);
-  if (p.prio_mode && p.dispatch_order) {
+  if (p.prio_mode && p.dispatch_order) {  // never taken (prio_mode is always 0): see EnvParams::dispatch_order
     const int pr = (int)((uint32_t)p.order[blockIdx.x] >> 24);
     if (pr == 3) __builtin_amdgcn_s_setprio(3);
     else if (pr == 2) __builtin_amdgcn_s_setprio(2);
@@ -2594,14 +2604,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
 #pragma unroll
     for (int u = 0; u < 12; ++u) a[u] = corner + ((u & 1) ? (ow[u >> 1] >> 16) : (ow[u >> 1] & 0xffffu));
 #pragma unroll
-    for (int u = 0; u < 12; ++u) w[u] = PROBE == 25 ? 0u : lds_ld(a[u]);
+    for (int u = 0; u < 12; ++u) w[u] = lds_ld(a[u]);
     const uint32_t own0 = (ow[0] & 0xffffu) == (uint32_t)OFF0, own1 = (ow[0] >> 16) == (uint32_t)OFF0;
     uint32_t stop = 0;
 #pragma unroll
     for (int u = 0; u < 12; ++u) {
       stop = u == 0 ? w[0] : or_b32(stop, w[u]);
       const uint32_t skip = u == 0 ? or_b32(stop, own0) : (u == 1 ? or_b32(stop, own1) : stop);
-      if (PROBE != 24) lds_st(__umul24(skip, (uint32_t)D) + a[u] + D, 1);
+      lds_st(__umul24(skip, (uint32_t)D) + a[u] + D, 1);
     }
   };
   // this tick's visibility into the cleared plane: every camera marches the shared fan's
@@ -2779,8 +2789,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
     const int par = k & 1;
     if ((k & 63) == 0) vact = k + lane < K ? L.act[k + lane] : 0u;
     // the DMA issued a tick ago (older than the previous tick's kStores stores) has landed
-    if (PROBE == 21) asm volatile("s_waitcnt vmcnt(63)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kStores) : "memory");
+    asm volatile("s_waitcnt vmcnt(%0)" ::"i"(kStores) : "memory");
     int n_uniq = 0, n_tie = 0;
     if (!ivl && wid == 0) {  // one LDS read for both header words
       const int2 h = *reinterpret_cast<const int2*>(&L.stg->hdr[2]);
@@ -2792,7 +2801,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
     const bool frozen = s.done != 0;  // finished, no auto-reset: environment.py:232-233
     double reward = 0.0;
     int status = kAlreadyDone, curr = 0;
-    if (!frozen && PROBE != 27) {
+    if (!frozen) {
       // 1. move (environment.py:239-246) and the reward terms that precede detection (:235, :261-269)
       const int a = __builtin_amdgcn_readlane((int)vact, k & 63);
       const int nr = s.pos_r + (a == 1 ? -1 : (a == 2 ? 1 : 0)), nc = s.pos_c + (a == 3 ? -1 : (a == 4 ? 1 : 0));
@@ -2821,7 +2830,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
       if (k + 1 < K && wid == 0) dma_next_cone(par ^ 1);  // tick k + 1's entry if the env still acts then
       LEAN_STAMP(1);  // 1: move, rotation, patrol
       // 3. visibility (environment.py:257-258)
-      if (PROBE != 22 && PROBE != 28) cast(k, n_uniq, n_tie, par, true, staged_wide);
+      cast(k, n_uniq, n_tie, par, true, staged_wide);
       LEAN_STAMP(3);  // 3: the cached guard cones (2: the cameras, inside cast)
     }
     // (tick k + 1's fan entry went out inside cast_fan; a frozen env keeps its plane and skips it)
@@ -2835,7 +2844,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
     }
     int done_now = s.done;
     LEAN_STAMP(4);  // 4: next fan DMA, the channel-1 quads
-    if (!frozen && PROBE != 27 && PROBE != 28) {
+    if (!frozen) {
       // 4. detection, vault, timeout (environment.py:271-297), in the reference's order
       bool seen;
       if constexpr (NW == 1) {
@@ -2914,16 +2923,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
       const int q = lane + 64 * (wid * QW + j);
       const bool in = q < N4;
       const int qc = in ? q : N4 - 1;
-      const uint32_t b = PROBE == 26 ? 0x01020304u : *reinterpret_cast<const uint32_t*>(L.grid + 4 * qc);
+      const uint32_t b = *reinterpret_cast<const uint32_t*>(L.grid + 4 * qc);
       // float32(tile) / 5 == float32(tile) * 0.2f for every tile type (environment.py:319)
-      if (PROBE == 23) continue;
       obs_put(rs, pol, in ? 16 * q : (int)kOOB,
               make_float4((float)(b & 0xff) * 0.2f, (float)((b >> 8) & 0xff) * 0.2f,
                           (float)((b >> 16) & 0xff) * 0.2f, (float)(b >> 24) * 0.2f));
       const uint32_t v = v1[j];
       obs_put(rs, pol, in ? 16 * (N4 + q) : (int)kOOB,
               make_float4((float)(v & 0xff), (float)((v >> 8) & 0xff), (float)((v >> 16) & 0xff), (float)(v >> 24)));
-      float4 c2 = PROBE == 26 ? make_float4(0.f, 0.f, 0.f, 0.f) : L.plane2[qc];
+      float4 c2 = L.plane2[qc];
       // the solver's cell of channel 2 is fl32(1 + g) for its static value g (heist_create's
       // second plane), unless it is the vault, whose value wins: patched in the register of
       // the lane that stores its quad (one store per quad, no second write of the line)
@@ -2976,8 +2984,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(HEIST_L
   }
 }
 
-template <int W, int U, int O, int D>
-__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) void reset_kernel(EnvParams p, const uint8_t* __restrict__ mask,
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(kStepOcc))) void reset_kernel(EnvParams p, const uint8_t* __restrict__ mask,
                                                         float* __restrict__ obs) {
   constexpr int NT = 64 * W;
   extern __shared__ __align__(16) unsigned char smem[];
@@ -3011,7 +3019,7 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(O))) voi
     E = guard_emit(gd);
   }
   publish_emitters(L, E, n_slot);
-  raycast_pass<NT, U, D>(p, e, smem, L, n_slot, mc);
+  raycast_pass<NT, D>(p, e, smem, L, n_slot, mc);
   write_obs<NT>(p, e, s, L, 0, obs);
   if (t == 0) p.scal[e] = s;
 }
@@ -3181,7 +3189,6 @@ __global__ __launch_bounds__(64) void set_layout_kernel(EnvParams p, int max_wal
 // kConeRange) keeps hslot = kUncached and is raycast live by step/reset.
 template <int D>
 __global__ __launch_bounds__(64) void guard_cone_kernel(EnvParams p, const uint8_t* __restrict__ mask) {
-  constexpr int U = 4;
   extern __shared__ __align__(16) unsigned char smem[];
   __shared__ double heads[kConeSlots];
   __shared__ uint8_t arr[kConePath];  // heading slot on entering patrol point j; kUncached: no move
@@ -3244,7 +3251,7 @@ __global__ __launch_bounds__(64) void guard_cone_kernel(EnvParams p, const uint8
     E.first = 0;
     E.kind = 1;
     E.members = 1;
-    for (int ray = lane; ray <= E.num_rays; ray += 64) exact_ray<U, D>(smem, E, ray, L.PC, 0, p.half_deg);
+    for (int ray = lane; ray <= E.num_rays; ray += 64) exact_ray<D>(smem, E, ray, L.PC, 0, p.half_deg);
     __syncthreads();
     if (lane < kConeEntry) {
       uint32_t bits = 0;
@@ -3291,7 +3298,6 @@ template <int D>
 __global__ __launch_bounds__(64) void cones_kernel(int R, int C, const uint8_t* __restrict__ walls,
                                                     const int32_t* __restrict__ meta, const double* __restrict__ params,
                                                     uint8_t* __restrict__ out, int ray_mode) {
-  constexpr int U = 4;
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = blockIdx.x;
   const int lane = threadIdx.x;
@@ -3315,7 +3321,7 @@ __global__ __launch_bounds__(64) void cones_kernel(int R, int C, const uint8_t* 
   __syncthreads();
   build_wall_map<64>(L.grid, L, R, C);
   __syncthreads();
-  cast_rays<64, U, D, false>(smem, L, ray_mode, 0, nullptr);
+  cast_rays<64, D, false>(smem, L, ray_mode, 0, nullptr);
   __syncthreads();
   for (int i = lane; i < RC; i += 64) {
     const int r = i / C;
@@ -3333,7 +3339,6 @@ __global__ __launch_bounds__(64) void cone_order_kernel(int R, int C, const uint
                                                          const int32_t* __restrict__ meta,
                                                          const double* __restrict__ params,
                                                          uint32_t* __restrict__ keys_out) {
-  constexpr int U = 4;
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = blockIdx.x;
   const int lane = threadIdx.x;
@@ -3356,7 +3361,7 @@ __global__ __launch_bounds__(64) void cone_order_kernel(int R, int C, const uint
   E.step = E.fov / (double)E.num_rays;
   E.first = 0;
   E.members = 1;
-  for (int ray = lane; ray <= E.num_rays; ray += 64) exact_ray<U, D, true>(smem, E, ray, L.PC, 0, nullptr, keys);
+  for (int ray = lane; ray <= E.num_rays; ray += 64) exact_ray<D, true>(smem, E, ray, L.PC, 0, nullptr, keys);
   __syncthreads();
   for (int i = lane; i < RC; i += 64) {
     const int r = i / C;
@@ -3460,33 +3465,9 @@ __global__ __launch_bounds__(1024) void order_kernel(EnvParams p) {
     }
   }
   __syncthreads();
-  // rank i (heaviest first) -> block.  dispatch_order 1: block i.  2 (snake draft): the
-  // K-tick kernels keep every block of a launch resident (16 per CU), the k-th block a CU
-  // receives (block n_cu * k + cu) lands on SIMD k % 4, and a SIMD's time is the sum of its 4
-  // envs' ticks -- so ranks are dealt to the 4 n_cu SIMDs round by round in alternating
-  // direction (round r = rank / (4 n_cu)), which evens the SIMD sums (heaviest-first alone
-  // gives SIMD 0 of every CU the heaviest env of each round); a last partial round keeps its
-  // ranks.
-  const int S = 4 * p.n_cu, full = p.dispatch_order == 2 && p.n_cu > 0 ? p.n_envs / S * S : 0;
-  for (int e = t; e < p.n_envs; e += 1024) {
-    const int i = atomicAdd(&bucket[key(e)], 1);
-    int b = i;
-    if (i < full) {
-      const int r = i / S, pos = i - r * S, sl = (r & 1) ? S - 1 - pos : pos;
-      const int cu = sl % p.n_cu, simd = sl / p.n_cu;
-      b = p.n_cu * (4 * r + simd) + cu;
-    }
-    // the wave priority (s_setprio) of the env's K-tick lean launch by cost rank i: the
-    // heaviest envs get the SIMD first, the light ones fill their latency gaps
-    // (prio_mode 1: quartiles 3 / 2 / 1 / 0; 2: top 1/16 -> 3, next 1/16 -> 2, next 1/8 -> 1;
-    // 3: top 1/8 -> 1)
-    const long long f16 = 16LL * i / (p.n_envs > 0 ? p.n_envs : 1);
-    int pr = 0;
-    if (p.prio_mode == 1) pr = 3 - (int)(f16 >> 2);
-    else if (p.prio_mode == 2) pr = f16 < 1 ? 3 : (f16 < 2 ? 2 : (f16 < 4 ? 1 : 0));
-    else if (p.prio_mode == 3) pr = f16 < 2 ? 1 : 0;
-    p.order[b] = e | (pr << 24);
-  }
+  // rank i (heaviest first) -> block i.  A snake draft of the ranks over the SIMDs and a wave
+  // priority by rank were measured and removed (profiles/r05e_configs_*, r05m_lean_ab.log).
+  for (int e = t; e < p.n_envs; e += 1024) p.order[atomicAdd(&bucket[key(e)], 1)] = e;
 }
 
 hipError_t launch_order(const EnvParams& p, hipStream_t st) {
@@ -3520,11 +3501,9 @@ hipError_t launch_set_layout(const EnvParams& p, int max_walls, const int32_t* w
   return hipGetLastError();
 }
 
-// (waves per env W, samples per ray chunk U, min waves per SIMD O, stop-map -> vis gap D)
-// variants; (2, 4, 8, D) is the default for either D.
-#define HEIST_ENV_VARIANTS(X) \
-  X(2, 4, 8, 1024) X(2, 4, 8, 2048) X(2, 4, 8, 6144) X(4, 4, 8, 1024) X(4, 4, 8, 2048) X(4, 4, 8, 6144) \
-  X(1, 4, 8, 1024)
+// (waves per env W, stop-map -> vis gap D) variants of step / reset; (2, D) is the default
+// for every D.
+#define HEIST_ENV_VARIANTS(X) X(2, 1024) X(2, 2048) X(2, 6144) X(4, 1024) X(4, 2048) X(4, 6144) X(1, 1024)
 
 // the plane gap D: 1024 up to 20 x 20, 2048 up to 33 x 33 (BASELINE C5's 32 x 32), 6144 up to 64 x 64
 int vis_gap_for(int R, int C) {
@@ -3532,9 +3511,9 @@ int vis_gap_for(int R, int C) {
   return b <= 1024 ? 1024 : (b <= 2048 ? 2048 : 6144);
 }
 
-bool env_variant_exists(int W, int U, int O, int D) {
-#define HEIST_HAS_CASE(W_, U_, O_, D_) \
-  if (W == W_ && U == U_ && O == O_ && D == D_) return true;
+bool env_variant_exists(int W, int D) {
+#define HEIST_HAS_CASE(W_, D_) \
+  if (W == W_ && D == D_) return true;
   HEIST_ENV_VARIANTS(HEIST_HAS_CASE)
 #undef HEIST_HAS_CASE
   return false;
@@ -3542,10 +3521,10 @@ bool env_variant_exists(int W, int U, int O, int D) {
 
 hipError_t launch_reset(const EnvParams& p, const uint8_t* mask, float* obs, hipStream_t st) {
   const size_t lds = env_lds(p);
-#define HEIST_RESET_CASE(W, U, O, D)                                                                    \
-  if (p.step_waves == W && p.ray_chunk == U && p.step_occ == O && p.vis_gap == D) {                    \
-    hipLaunchKernelGGL((reset_kernel<W, U, O, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, mask, obs); \
-    return hipGetLastError();                                                                          \
+#define HEIST_RESET_CASE(W, D)                                                                    \
+  if (p.step_waves == W && p.vis_gap == D) {                                                      \
+    hipLaunchKernelGGL((reset_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, mask, obs); \
+    return hipGetLastError();                                                                     \
   }
   HEIST_ENV_VARIANTS(HEIST_RESET_CASE)
 #undef HEIST_RESET_CASE
@@ -3555,8 +3534,8 @@ hipError_t launch_reset(const EnvParams& p, const uint8_t* mask, float* obs, hip
 // The profiling variant (HEIST_PROBE_MODE != 0) exists for the default 20 x 20 geometry only.
 static hipError_t launch_step_probe(const EnvParams& p, const int64_t* actions, float* obs, float* rew, double* rew64,
                                     uint8_t* done_out, int8_t* status_out, int auto_reset, size_t lds, hipStream_t st) {
-  if (p.step_waves != 2 || p.ray_chunk != 4 || p.step_occ != 8 || p.vis_gap != 1024) return hipErrorInvalidValue;
-  hipLaunchKernelGGL((step_kernel<2, 4, 8, 1024, false, false, true>), dim3(p.n_envs), dim3(128), lds, st, p, actions,
+  if (p.step_waves != 2 || p.vis_gap != 1024) return hipErrorInvalidValue;
+  hipLaunchKernelGGL((step_kernel<2, 1024, false, false, true>), dim3(p.n_envs), dim3(128), lds, st, p, actions,
                      obs, rew, rew64, done_out, status_out, auto_reset);
   return hipGetLastError();
 }
@@ -3564,36 +3543,35 @@ static hipError_t launch_step_probe(const EnvParams& p, const int64_t* actions, 
 hipError_t launch_step(const EnvParams& p, const int64_t* actions, float* obs, float* rew, double* rew64,
                        uint8_t* done_out, int8_t* status_out, int auto_reset, hipStream_t st) {
   const size_t lds = env_lds(p);
-#define HEIST_STEP_CASE(W, U, O, D)                                                                       \
-  if (p.step_waves == W && p.ray_chunk == U && p.step_occ == O && p.vis_gap == D) {                      \
-    if (p.probe_mode)                                                                                    \
-      return launch_step_probe(p, actions, obs, rew, rew64, done_out, status_out, auto_reset, lds, st);  \
-    if (p.stamps)                                                                                        \
-      hipLaunchKernelGGL((step_kernel<W, U, O, D, true, false>), dim3(p.n_envs), dim3(64 * W), lds, st, p, \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                    \
-    else if (p.sample_counter || p.redo_counter)                                                         \
-      hipLaunchKernelGGL((step_kernel<W, U, O, D, false, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p, \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                    \
-    else                                                                                                 \
-      hipLaunchKernelGGL((step_kernel<W, U, O, D, false, false>), dim3(p.n_envs), dim3(64 * W), lds, st, p, \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                    \
-    return hipGetLastError();                                                                            \
+#define HEIST_STEP_CASE(W, D)                                                                             \
+  if (p.step_waves == W && p.vis_gap == D) {                                                              \
+    if (p.probe_mode)                                                                                     \
+      return launch_step_probe(p, actions, obs, rew, rew64, done_out, status_out, auto_reset, lds, st);   \
+    if (p.stamps)                                                                                         \
+      hipLaunchKernelGGL((step_kernel<W, D, true, false>), dim3(p.n_envs), dim3(64 * W), lds, st, p,      \
+                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                     \
+    else if (p.sample_counter || p.redo_counter)                                                          \
+      hipLaunchKernelGGL((step_kernel<W, D, false, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p,      \
+                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                     \
+    else                                                                                                  \
+      hipLaunchKernelGGL((step_kernel<W, D, false, false>), dim3(p.n_envs), dim3(64 * W), lds, st, p,     \
+                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                     \
+    return hipGetLastError();                                                                             \
   }
   HEIST_ENV_VARIANTS(HEIST_STEP_CASE)
 #undef HEIST_STEP_CASE
   return hipErrorInvalidValue;
 }
 
-// K ticks per launch: the (W, U, O, D) variants below, for grids with C % 4 == 0 (the
+// K ticks per launch: the (W, D) variants below, for grids with C % 4 == 0 (the
 // observation rows go out as float4 quads that never cross a grid row); another
 // configuration runs K single-tick launches instead (same results).
 #define HEIST_MULTI_VARIANTS(X) \
-  X(2, 4, 8, 1024) X(2, 4, 8, 2048) X(2, 4, 8, 6144) X(4, 4, 8, 1024) X(4, 4, 8, 2048) X(4, 4, 8, 6144) \
-  X(1, 4, 4, 1024) X(1, 4, 4, 2048) X(2, 4, 6, 1024) X(2, 4, 7, 1024) X(1, 4, 5, 1024) X(1, 4, 6, 1024)
+  X(2, 1024) X(2, 2048) X(2, 6144) X(4, 1024) X(4, 2048) X(4, 6144) X(1, 1024) X(1, 2048)
 
-bool multi_variant_exists(int W, int U, int O, int D) {
-#define HEIST_HAS_MULTI(W_, U_, O_, D_) \
-  if (W == W_ && U == U_ && O == O_ && D == D_) return true;
+bool multi_variant_exists(int W, int D) {
+#define HEIST_HAS_MULTI(W_, D_) \
+  if (W == W_ && D == D_) return true;
   HEIST_MULTI_VARIANTS(HEIST_HAS_MULTI)
 #undef HEIST_HAS_MULTI
   return false;
@@ -3608,89 +3586,100 @@ size_t step_multi_lds(const EnvParams& p, int K) {
 
 // Two waves per env for the 32 x 32 lean kernel (HEIST_LEAN_WAVES: 0 auto, 1, 2): auto when
 // the batch's doubled waves still fit the chip at the kernel's 4 waves per SIMD.
-bool lean_two_waves(const EnvParams& p) {
+static bool lean_two_waves(const EnvParams& p) {
   if (p.lean_waves != 0) return p.lean_waves == 2;
   return 2 * (size_t)p.n_envs <= 16 * (size_t)(p.n_cu > 0 ? p.n_cu : 256);
+}
+
+// What a heist_step_multi launch on p runs (MultiRoute, heist_device.h): the one place that
+// decides it, for launch_step_multi and for heist_capi.hip's fan-table bookkeeping, one-tick
+// heist_step route and heist_get_config.
+MultiRoute multi_route(const EnvParams& p) {
+  MultiRoute r{MultiRoute::kSingleTicks, 0, p.step_waves, p.stamps != nullptr};
+  // profiling variants of the generic kernel: modes 1-4, the default 20 x 20 geometry only
+  // (the other modes are the single-tick kernel's)
+  if (p.probe_mode >= 1 && p.probe_mode <= 4 && p.vis_gap == 1024 && (p.multi_waves == 1 || p.multi_waves == 2)) {
+    r.kind = MultiRoute::kProbe;
+    r.waves = p.multi_waves;
+    return r;
+  }
+  // the K-tick kernels neither probe nor count (the step kernel's counting variant does)
+  if (p.probe_mode != 0 || p.sample_counter || p.redo_counter) return r;
+  // the lean kernel (step_lean_kernel): 20 x 20 at one wave per env; 32 x 32 at any batch
+  // size -- its lean form is one wave per env whatever multi_waves says (two where they fit
+  // the chip, plain form only), the envs it cannot serve taking the one-wave generic body
+  const bool lean20 = p.multi_waves == 1 && p.R == 20 && p.C == 20 && p.vis_gap == 1024;
+  const bool lean32 = p.R == 32 && p.C == 32 && p.vis_gap == 2048;
+  if (p.lean && (lean20 || lean32) && p.max_cams + p.max_guards <= kMaxEmitters) {
+    r.kind = MultiRoute::kLean;
+    r.grid = lean20 ? 20 : 32;
+    r.waves = lean32 && !r.stamped && lean_two_waves(p) ? 2 : 1;
+    return r;
+  }
+  if (multi_variant_exists(p.multi_waves, p.vis_gap) && (p.C & 3) == 0) {
+    r.kind = MultiRoute::kGeneric;
+    r.waves = p.multi_waves;
+  }
+  return r;
 }
 
 hipError_t launch_step_multi(const EnvParams& p, int K, const int64_t* actions, float* obs,
                              float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
                              hipStream_t st) {
+  const MultiRoute r = multi_route(p);
+  if (r.kind == MultiRoute::kSingleTicks) {
+    const size_t n = (size_t)p.n_envs;
+    for (int k = 0; k < K; ++k) {
+      const hipError_t e = launch_step(p, actions + k * n, obs + k * n * 3 * p.RC, rew + k * n, rew64 ? rew64 + k * n : nullptr,
+                                       done_out + k * n, status_out + k * n, auto_reset, st);
+      if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+  }
   const size_t lds = step_multi_lds(p, K);
-  if (p.probe_mode >= 1 && p.probe_mode <= 4 && p.ray_chunk == 4 && p.vis_gap == 1024 &&
-      ((p.multi_waves == 2 && p.multi_occ == 8) || (p.multi_waves == 1 && p.multi_occ == 4))) {
-    // profiling variants (default 20 x 20 geometry only)
-#define HEIST_PROBE_CASE(W_, O_, M)                                                                              \
-  if (p.multi_waves == W_ && p.probe_mode == M)                                                                \
-    hipLaunchKernelGGL((step_multi_kernel<W_, 4, O_, 1024, false, M>), dim3(p.n_envs), dim3(64 * W_), lds, st, p, K, \
+  if (r.kind == MultiRoute::kProbe) {
+#define HEIST_PROBE_CASE(W_, M)                                                                              \
+  if (p.multi_waves == W_ && p.probe_mode == M)                                                              \
+    hipLaunchKernelGGL((step_multi_kernel<W_, 1024, false, M>), dim3(p.n_envs), dim3(64 * W_), lds, st, p, K, \
                        actions, obs, rew, rew64, done_out, status_out, auto_reset);
-    HEIST_PROBE_CASE(2, 8, 1) HEIST_PROBE_CASE(2, 8, 2) HEIST_PROBE_CASE(2, 8, 3) HEIST_PROBE_CASE(2, 8, 4)
-    HEIST_PROBE_CASE(1, 4, 1) HEIST_PROBE_CASE(1, 4, 2) HEIST_PROBE_CASE(1, 4, 3) HEIST_PROBE_CASE(1, 4, 4)
+    HEIST_PROBE_CASE(2, 1) HEIST_PROBE_CASE(2, 2) HEIST_PROBE_CASE(2, 3) HEIST_PROBE_CASE(2, 4)
+    HEIST_PROBE_CASE(1, 1) HEIST_PROBE_CASE(1, 2) HEIST_PROBE_CASE(1, 3) HEIST_PROBE_CASE(1, 4)
 #undef HEIST_PROBE_CASE
     return hipGetLastError();
   }
-  // the lean one-wave kernel (step_lean_kernel): the default for 20 x 20 grids at one wave per env
-  // (20 x 20 at one wave per env; 32 x 32 at any batch size: its lean form is one wave per env
-  // whatever multi_waves says, the envs it cannot serve taking the one-wave generic body)
-  const bool lean20 = p.multi_waves == 1 && p.R == 20 && p.C == 20 && p.vis_gap == 1024;
-  const bool lean32 = p.R == 32 && p.C == 32 && p.vis_gap == 2048;
-#ifdef HEIST_LEAN_PROBES  // profiling variants of the lean kernel (tools/build_variant.sh ... -DHEIST_LEAN_PROBES)
-  if (p.lean && lean20 && p.probe_mode >= 21 && p.probe_mode <= 28 && !p.stamps &&
-      p.max_cams + p.max_guards <= kMaxEmitters) {
-    if (p.fan_on && p.fan_fill) hipLaunchKernelGGL(fan_kernel, dim3(kFanTicks), dim3(kFanRays), 0, st, p);
+  if (p.fan_on && p.fan_fill) hipLaunchKernelGGL(fan_kernel, dim3(kFanTicks), dim3(kFanRays), 0, st, p);
+  if (r.kind == MultiRoute::kLean) {
     const size_t lds_l = lean_lds_bytes(p, K);
-#define HEIST_LEAN_PROBE(M)                                                                                       \
-  if (p.probe_mode == M)                                                                                          \
-    hipLaunchKernelGGL((step_lean_kernel<20, 20, false, M>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, \
-                       rew, rew64, done_out, status_out, auto_reset);
-    HEIST_LEAN_PROBE(21) HEIST_LEAN_PROBE(22) HEIST_LEAN_PROBE(23) HEIST_LEAN_PROBE(24) HEIST_LEAN_PROBE(25)
-    HEIST_LEAN_PROBE(26) HEIST_LEAN_PROBE(27) HEIST_LEAN_PROBE(28)
-#undef HEIST_LEAN_PROBE
-    return hipGetLastError();
-  }
-#endif
-  if (p.lean && (lean20 || lean32) && p.probe_mode == 0 && !p.sample_counter && !p.redo_counter &&
-      p.max_cams + p.max_guards <= kMaxEmitters) {
-    if (p.fan_on && p.fan_fill) hipLaunchKernelGGL(fan_kernel, dim3(kFanTicks), dim3(kFanRays), 0, st, p);
-    const size_t lds_l = lean_lds_bytes(p, K);
-    if (lean20 && p.stamps)
+    if (r.grid == 20 && r.stamped)
       hipLaunchKernelGGL((step_lean_kernel<20, 20, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
                          rew64, done_out, status_out, auto_reset);
-    else if (lean20)
+    else if (r.grid == 20)
       hipLaunchKernelGGL((step_lean_kernel<20, 20>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew, rew64,
                          done_out, status_out, auto_reset);
-    else if (p.stamps)
+    else if (r.stamped)
       hipLaunchKernelGGL((step_lean_kernel<32, 32, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
                          rew64, done_out, status_out, auto_reset);
-    else if (lean_two_waves(p))
-      hipLaunchKernelGGL((step_lean_kernel<32, 32, false, 0, 2>), dim3(p.n_envs), dim3(128), lds_l, st, p, K, actions,
+    else if (r.waves == 2)
+      hipLaunchKernelGGL((step_lean_kernel<32, 32, false, 2>), dim3(p.n_envs), dim3(128), lds_l, st, p, K, actions,
                          obs, rew, rew64, done_out, status_out, auto_reset);
     else
       hipLaunchKernelGGL((step_lean_kernel<32, 32>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
                          rew64, done_out, status_out, auto_reset);
     return hipGetLastError();
   }
-#define HEIST_MULTI_CASE(W, U, O, D)                                                                        \
-  if (p.multi_waves == W && p.ray_chunk == U && p.multi_occ == O && p.vis_gap == D && p.probe_mode == 0 && \
-      !p.sample_counter && !p.redo_counter && (p.C & 3) == 0) {                                            \
-    if (p.fan_on && p.fan_fill) hipLaunchKernelGGL(fan_kernel, dim3(kFanTicks), dim3(kFanRays), 0, st, p);   \
-    if (p.stamps)                                                                                            \
-      hipLaunchKernelGGL((step_multi_kernel<W, U, O, D, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,  \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                         \
-    else                                                                                                     \
-      hipLaunchKernelGGL((step_multi_kernel<W, U, O, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,        \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                         \
-    return hipGetLastError();                                                                                \
+#define HEIST_MULTI_CASE(W, D)                                                                             \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                              \
+    if (r.stamped)                                                                                         \
+      hipLaunchKernelGGL((step_multi_kernel<W, D, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,     \
+                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                      \
+    else                                                                                                   \
+      hipLaunchKernelGGL((step_multi_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,           \
+                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                      \
+    return hipGetLastError();                                                                              \
   }
   HEIST_MULTI_VARIANTS(HEIST_MULTI_CASE)
 #undef HEIST_MULTI_CASE
-  const size_t n = (size_t)p.n_envs;  // no K-tick variant (or instrumentation armed): K single-tick launches
-  for (int k = 0; k < K; ++k) {
-    const hipError_t e = launch_step(p, actions + k * n, obs + k * n * 3 * p.RC, rew + k * n, rew64 ? rew64 + k * n : nullptr,
-                                     done_out + k * n, status_out + k * n, auto_reset, st);
-    if (e != hipSuccess) return e;
-  }
-  return hipSuccess;
+  return hipErrorInvalidValue;  // not reached: multi_route only names a variant that exists
 }
 
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

@@ -1036,6 +1036,30 @@ def test_step_lean_32x32_shared_fan_and_interval_mix(gpu_device, monkeypatch, wa
         assert torch.equal(sa[key], sb[key]), key
 
 
+def test_lean_waves_reports_the_kernel_that_runs(gpu_device, monkeypatch):
+    """kernel_config()["lean_waves"] is the wave count of the lean kernel a heist_step_multi
+    launch would run now: 2 for a 64-env 32 x 32 handle (auto: the doubled waves fit the chip),
+    1 while stamps are armed (the stamped instance is one wave per env), 2 again once they are
+    disarmed, and 1 for a handle the lean kernel does not serve (HEIST_LEAN=0)."""
+    from heist_amd import _native as nat
+    cfg = EnvironmentConfig(grid_rows=32, grid_cols=32)
+    a = HeistEnv(64, cfg, device=gpu_device)
+    assert a.kernel_config()["lean"] == 1 and a.kernel_config()["lean_waves"] == 2
+    L = nat.lib()
+    words = max(int(L.heist_stamp_words(a._h, 0)), int(L.heist_stamp_words(a._h, 1)))
+    buf = torch.zeros(words, dtype=torch.int64, device=gpu_device)
+    nat.check(L.heist_step_stamps(a._h, nat.ptr(buf), buf.numel()), "heist_step_stamps")
+    try:
+        assert a.kernel_config()["lean_waves"] == 1
+    finally:
+        nat.check(L.heist_step_stamps(a._h, None, 0), "heist_step_stamps")
+    assert a.kernel_config()["lean_waves"] == 2
+    monkeypatch.setenv("HEIST_LEAN", "0")
+    b = HeistEnv(64, cfg, device=gpu_device)
+    monkeypatch.delenv("HEIST_LEAN")
+    assert b.kernel_config()["lean"] == 0 and b.kernel_config()["lean_waves"] == 1
+
+
 def test_step_lean_interval_fans_on_architect_layouts(gpu_device, monkeypatch):
     """The headline's Architect layouts with the shared fan table off (HEIST_SHARED_FAN=0):
     every env takes the interval fans instead; == single ticks, 60 ticks."""

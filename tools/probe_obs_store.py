@@ -1,6 +1,6 @@
 """heist_step timing by a handle knob read at heist_create (PROBE_VAR, default
 HEIST_OBS_STORE: 0 plain, 1 write-through sc1, 2 nt, 3 sc1 nt observation stores; or e.g.
-HEIST_DISPATCH_ORDER 0/1) at 4096 envs on the bench's C2 layouts (fixed Architect
+HEIST_SPLIT_OBS 0/1) at 4096 envs on the bench's C2 layouts (fixed Architect
 checkpoint, budget 15).  Rounds interleave the policies so clock
 and thermal drift hit all of them alike; every policy must give the same observations.
 One JSON line per policy."""

@@ -12,10 +12,8 @@ from heist_amd import EnvironmentConfig, HeistEnv  # noqa: E402
 from heist_amd.layouts import synthetic_layouts  # noqa: E402
 
 
-def make(n, budget, n_cams, n_guards, R=20, waves=4, chunk=4, occ=1):
+def make(n, budget, n_cams, n_guards, R=20, waves=4):
     os.environ["HEIST_STEP_WAVES"] = str(waves)
-    os.environ["HEIST_RAY_CHUNK"] = str(chunk)
-    os.environ["HEIST_STEP_OCC"] = str(occ)
     cfg = EnvironmentConfig(grid_rows=R, grid_cols=R)
     env = HeistEnv(n, cfg, device="cuda")
     lays = synthetic_layouts(n, R, R, budget, seed=1, n_cams=n_cams, n_guards=n_guards)
@@ -39,13 +37,11 @@ def time_env(env, acts, iters=40):
 
 
 cases = {}
-for occ in (1, 8):  # min waves per SIMD the step kernel is compiled for
-    for n in (4096, 16384):
-        cases["o%d_n%d_b15" % (occ, n)] = make(n, 15, None, None, occ=occ)
-    cases["o%d_n4096_c4_g0" % occ] = make(4096, 14, 4, 0, occ=occ)
-    cases["o%d_n4096_c0_g2" % occ] = make(4096, 12, 0, 2, occ=occ)
-for k in ("HEIST_RAY_CHUNK", "HEIST_STEP_WAVES", "HEIST_STEP_OCC"):
-    os.environ.pop(k, None)
+for n in (4096, 16384):
+    cases["n%d_b15" % n] = make(n, 15, None, None)
+cases["n4096_c4_g0"] = make(4096, 14, 4, 0)
+cases["n4096_c0_g2"] = make(4096, 12, 0, 2)
+os.environ.pop("HEIST_STEP_WAVES", None)
 res = {k: [] for k in cases}
 for rnd in range(5):
     for k, (env, acts) in cases.items():

@@ -1,6 +1,6 @@
 """heist_step timing across the compiled launch variants at 4096 envs (bench layouts):
-waves per env, samples per ray chunk, the waves-per-SIMD bound the kernel is compiled for.
-Env vars are read at heist_create.  One JSON line per variant."""
+waves per env, fast or exact rays.  Env vars are read at heist_create.  One JSON line per
+variant."""
 import json
 import os
 import sys
@@ -13,10 +13,10 @@ from heist_amd import EnvironmentConfig, HeistEnv  # noqa: E402
 from heist_amd.layouts import valid_synthetic_layouts  # noqa: E402
 
 VARIANTS = {  # the compiled variants (HEIST_ENV_VARIANTS in heist_env.hip)
-    "w2_u4_o8": {"HEIST_STEP_WAVES": "2", "HEIST_STEP_OCC": "8"},
-    "w2_u4_o8_exact": {"HEIST_STEP_WAVES": "2", "HEIST_EXACT_RAYS": "1"},
-    "w4_u4_o8": {"HEIST_STEP_WAVES": "4", "HEIST_STEP_OCC": "8"},
-    "w1_u4_o8": {"HEIST_STEP_WAVES": "1", "HEIST_STEP_OCC": "8"},
+    "w2": {"HEIST_STEP_WAVES": "2"},
+    "w2_exact": {"HEIST_STEP_WAVES": "2", "HEIST_EXACT_RAYS": "1"},
+    "w4": {"HEIST_STEP_WAVES": "4"},
+    "w1": {"HEIST_STEP_WAVES": "1"},
 }
 
 
@@ -24,7 +24,7 @@ def main():
     n = int(os.environ.get("PROBE_N", "4096"))
     envs = {}
     for name, ev in VARIANTS.items():
-        for k in ("HEIST_STEP_WAVES", "HEIST_RAY_CHUNK", "HEIST_STEP_OCC", "HEIST_EXACT_RAYS"):
+        for k in ("HEIST_STEP_WAVES", "HEIST_EXACT_RAYS"):
             os.environ.pop(k, None)
         os.environ.update(ev)
         env = HeistEnv(n, EnvironmentConfig(), max_cams=8, max_guards=4, max_path=16, device="cuda", auto_reset=True)
