@@ -388,7 +388,8 @@ int heist_relu_bwd_nhwc(float* g, const float* y, int n, int positions, int chan
  * fp32), for the PPO update's forward and backward (agents/solver.py:157-199 over
  * networks.py:93-100): every pass of relu(conv1) -> relu(conv2) -> relu(conv3) -> pool as one
  * persistent kernel with the weights in registers and the activation bands in LDS, replacing
- * MIOpen's convolutions.  20 x 20 grids (heist_train_conv_supported).  Activations are
+ * MIOpen's convolutions.  20 x 20 and 32 x 32 grids (heist_train_conv_supported: bands of 4
+ * and of 2 image rows per work unit; any other size is rejected).  Activations are
  * [n][rows][cols][P] float32 with P = channels + 4 (the 4 pad words are never read), the
  * network input [n][rows][cols][4] (heist_train_obs_nhwc4), all 16-byte aligned.
  *   heist_train_conv_pack: torch weights [co][ci][3][3] of layer 1 (3 -> 32, mode 0), 2 (32 -> 64)

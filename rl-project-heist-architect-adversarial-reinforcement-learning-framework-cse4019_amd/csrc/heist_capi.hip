@@ -69,6 +69,7 @@ int64_t arch_update_workspace_bytes();
 hipError_t launch_arch_update(float* const* p, float* const* m, float* const* v, const float* grid, int R, int C,
                               const float* target, int k, const float* adam_sc, float* vloss, void* ws, double beta1,
                               double beta2, double eps, double max_norm, double value_coeff, hipStream_t st);
+bool train_conv_grid_supported(int R, int C);
 int train_conv_frag_floats(int layer, int mode);
 int64_t train_conv_partial_floats(int layer, int n, int R, int C);
 hipError_t launch_train_conv_pack(int layer, int mode, const float* w, float* frag, hipStream_t st);
@@ -824,7 +825,7 @@ int heist_relu_bwd_nhwc(float* g, const float* y, int n, int positions, int chan
                    "heist_relu_bwd_nhwc");
 }
 
-int heist_train_conv_supported(int rows, int cols) { return rows == 20 && cols == 20 ? 1 : 0; }
+int heist_train_conv_supported(int rows, int cols) { return heist::train_conv_grid_supported(rows, cols) ? 1 : 0; }
 
 int heist_train_conv_frag_floats(int layer, int mode) {
   if (!((layer == 1 && mode == 0) || ((layer == 2 || layer == 3) && (mode == 0 || mode == 1)))) return -1;
@@ -839,7 +840,7 @@ int heist_train_conv_pack(int layer, int mode, const float* w, float* frag, heis
 
 int heist_train_conv(int layer, int mode, const float* x, int n, int rows, int cols, const float* frag,
                      const float* bias, uint8_t* mask_bits, float* y, int* queue, heist_stream_t stream) {
-  HEIST_REQUIRE(heist_train_conv_supported(rows, cols), "heist_train_conv: grid must be 20x20");
+  HEIST_REQUIRE(heist_train_conv_supported(rows, cols), "heist_train_conv: grid must be 20x20 or 32x32");
   HEIST_REQUIRE(heist_train_conv_frag_floats(layer, mode) > 0, "heist_train_conv: layer 1 (mode 0), 2 or 3");
   HEIST_REQUIRE(n >= 0, "heist_train_conv: n < 0");
   HEIST_REQUIRE(x && frag && y && queue, "heist_train_conv: null pointer");
@@ -858,7 +859,7 @@ int64_t heist_train_conv_partial_floats(int layer, int n, int rows, int cols) {
 
 int heist_train_conv_wgrad(int layer, const float* dy, const float* x, int n, int rows, int cols, float* partial,
                            float* dw, float* db, int* queue, heist_stream_t stream) {
-  HEIST_REQUIRE(heist_train_conv_supported(rows, cols), "heist_train_conv_wgrad: grid must be 20x20");
+  HEIST_REQUIRE(heist_train_conv_supported(rows, cols), "heist_train_conv_wgrad: grid must be 20x20 or 32x32");
   HEIST_REQUIRE(layer >= 1 && layer <= 3, "heist_train_conv_wgrad: layer 1, 2 or 3");
   HEIST_REQUIRE(n >= 1, "heist_train_conv_wgrad: n < 1");
   HEIST_REQUIRE(dy && x && partial && dw && db && queue, "heist_train_conv_wgrad: null pointer");

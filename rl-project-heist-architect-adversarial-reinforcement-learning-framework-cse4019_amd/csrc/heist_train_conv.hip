@@ -15,7 +15,10 @@
 // 16-byte reads are bank-conflict free (16 lanes at a 272- or 144-byte position pitch cover
 // all 64 banks).  The network input (3 channels) is [n][R][C][4], channel 3 zero.
 //
-// Work.  A unit is a BAND: 4 output rows of one sample (4C positions = C/4 tiles of 16).  The
+// Work.  A unit is a BAND: BR output rows of one sample (BR C positions = BR C / 16 tiles of
+// 16): BR = 4 at 20 x 20 (5 tiles), BR = 2 at 32 x 32 (4 tiles; a 4-row band there would be 8
+// tiles, whose accumulators and activation registers beside 144 weight registers do not fit
+// in 256 VGPRs, and whose weight-gradient images do not fit in the CU's 160 KB of LDS).  The
 // kernels are persistent (one 512-thread workgroup per CU) and draw units from an atomic
 // queue, so a kernel that shares the chip with another (the Architect's update kernel holds
 // 64 CUs beside the Solver's update, training.py) keeps every CU it gets busy; every output
@@ -25,8 +28,8 @@
 //    D[co][pos] = sum over (tap, ci) of W[co][tap][ci] * X[pos + tap][ci]: the weights are the
 //    MFMA's A operand, held in VGPRs for the whole kernel (144 per lane at 64 -> 64), the
 //    activations its B operand, one ds_read_b128 feeding 4 MFMA k-steps.  Wave w owns one
-//    16-channel output tile of one band of the unit for all its C/4 position tiles; a lane ends
-//    with 4 consecutive channels of one position per tile (one 16-byte store).  (The transposed
+//    16-channel output tile of one band of the unit for all its BR C / 16 position tiles; a lane
+//    ends with 4 consecutive channels of one position per tile (one 16-byte store).  (The transposed
 //    orientation, D[pos][co] with the activations as A, would let a pool MFMA sum over the
 //    positions of D's rows; measured 3-8 % slower on every pass, it was not kept.)  Epilogue:
 //    forward  y = relu(D + bias) (torch: conv + b rounded, then max(., 0)), and the ReLU mask bits;
@@ -37,8 +40,9 @@
 //    dW[co][tap][ci] = sum over samples and positions of dY[pos][co] * X[pos + tap][ci], and
 //    db[co] = sum of dY[pos][co] (one more MFMA tile whose B operand is 1.0): positions are
 //    the MFMA's k (4 per k-step), each wave accumulates one 16-channel row tile of dW over a
-//    CHUNK of 40 bands in registers and writes it as that chunk's partial; conv_w_reduce
-//    sums the partials in chunk order (deterministic, no float atomics).
+//    CHUNK of bands (chunk_bands: 40 at BR = 4, 48 at BR = 2) in registers and writes it as that
+//    chunk's partial; conv_w_reduce sums the partials in chunk order (deterministic, no float
+//    atomics).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,7 +62,10 @@ typedef float f2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kThreads = 512;  // 8 waves, 2 per SIMD
-constexpr int kChunkBands = 40;  // bands per weight-gradient partial (8 samples of 20 rows)
+// bands per weight-gradient partial: 40 bands of 4 rows (8 samples of 20 rows, 3,200 positions),
+// 48 bands of 2 rows (3 samples of 32 rows, 3,072 positions); a multiple of every BPI
+template <int BR>
+constexpr int chunk_bands = BR == 4 ? 40 : 48;
 
 template <int CH>
 struct Pitch {
@@ -157,15 +164,15 @@ __device__ __forceinline__ void zero_range(float* dst, int bytes, int wid, int l
     *reinterpret_cast<f4*>(reinterpret_cast<char*>(dst) + off) = f4{0.f, 0.f, 0.f, 0.f};
 }
 
-// Input band image of band gb (sample gb / NB, output rows 4(gb % NB) .. +3) into LDS
-// `img` [6][C + 2][PI]: padded row rr <- image row y0 - 1 + rr, interior columns only (the
+// Input band image of band gb (sample gb / NB, output rows BR (gb % NB) .. + BR - 1) into LDS
+// `img` [BR + 2][C + 2][PI]: padded row rr <- image row y0 - 1 + rr, interior columns only (the
 // two border columns were zeroed once); rows outside the image are zeroed.
-template <int CI, int R, int C>
+template <int CI, int R, int C, int BR>
 __device__ __forceinline__ void load_band(const float* x, float* img, int gb, int piece0, int wid, int lane) {
-  constexpr int PI = Pitch<CI>::v, RP = C + 2, NB = R / 4, ROWB = C * PI * 4;
-  const int smp = gb / NB, y0 = (gb % NB) * 4;
+  constexpr int PI = Pitch<CI>::v, RP = C + 2, NB = R / BR, ROWB = C * PI * 4;
+  const int smp = gb / NB, y0 = (gb % NB) * BR;
 #pragma unroll
-  for (int rr = 0; rr < 6; ++rr) {
+  for (int rr = 0; rr < BR + 2; ++rr) {
     const int y = y0 - 1 + rr;
     float* dst = img + (rr * RP + 1) * PI;
     if (y >= 0 && y < R)
@@ -195,25 +202,26 @@ struct ConvAArgs {
   int n;
 };
 
-template <int CI, int CO, int S, int MODE, int R, int C>
+template <int CI, int CO, int S, int MODE, int R, int C, int BR>
 struct ConvAGeom {
   static constexpr int PI = Pitch<CI>::v, PO = Pitch<CO>::v, NCT = CO / 16, BPU = 8 / (NCT * S);
-  static constexpr int PT = C / 4, RP = C + 2, NB = R / 4;
-  static constexpr int BAND_F = 6 * RP * PI, BUF_F = BPU * BAND_F;
-  static constexpr int MASK_B = 4 * C * CO / 4;            // mask bytes per band (MODE 1)
+  static constexpr int PT = BR * C / 16, RP = C + 2, NB = R / BR;
+  static constexpr int BAND_F = (BR + 2) * RP * PI, BUF_F = BPU * BAND_F;
+  static constexpr int MASK_B = BR * C * CO / 4;           // mask bytes per band (MODE 1)
   static constexpr int MASK_F = MODE == 1 ? BPU * MASK_B / 4 : 0;  // floats per buffer
   static constexpr int KBW = CI == 4 ? 1 : (CI / 16) / S;  // 16-channel blocks per tap of a wave
   static constexpr int NWR = CI == 4 ? 9 : 36 * KBW;       // weight registers per lane
   static constexpr int LDS = 2 * (BUF_F + MASK_F) * 4 + 64;
   static_assert(NCT * S * BPU == 8, "8 waves");
   static_assert(MASK_B % 16 == 0, "mask rows are whole DMA lanes");
-  static_assert(C % 4 == 0 && R % 4 == 0, "bands of 4 rows, tiles of 16 positions");
-  static_assert(S == 1 || (PT * 256 <= C * PI && BPU * NCT <= 6), "a wave's k-split partials fit in a row interior");
+  static_assert(R % BR == 0 && (BR * C) % 16 == 0, "bands of BR rows, tiles of 16 positions");
+  static_assert(S == 1 || (PT * 256 <= C * PI && BPU * NCT <= BR + 2), "a wave's k-split partials fit in a row interior");
+  static_assert(LDS <= 160 * 1024, "the CU's LDS");
 };
 
-template <int CI, int CO, int S, int MODE, int R, int C>
+template <int CI, int CO, int S, int MODE, int R, int C, int BR>
 __global__ __launch_bounds__(kThreads, 1) void conv_a_kernel(ConvAArgs a) {
-  using G = ConvAGeom<CI, CO, S, MODE, R, C>;
+  using G = ConvAGeom<CI, CO, S, MODE, R, C, BR>;
   constexpr int PI = G::PI, PO = G::PO, NCT = G::NCT, BPU = G::BPU, PT = G::PT, RP = G::RP, NB = G::NB;
   constexpr int KBW = G::KBW, NWR = G::NWR;
   extern __shared__ f4 smem4[];
@@ -260,9 +268,9 @@ __global__ __launch_bounds__(kThreads, 1) void conv_a_kernel(ConvAArgs a) {
     for (int bb = 0; bb < BPU; ++bb) {
       const int gb = u * BPU + bb;
       if (gb >= nbands) continue;
-      load_band<CI, R, C>(a.x, buf[par] + bb * G::BAND_F, gb, bb * 7, wid, lane);
+      load_band<CI, R, C, BR>(a.x, buf[par] + bb * G::BAND_F, gb, bb * 7, wid, lane);
       if constexpr (MODE == 1) {
-        const int smp = gb / NB, y0 = (gb % NB) * 4;
+        const int smp = gb / NB, y0 = (gb % NB) * BR;
         dma_range(reinterpret_cast<const float*>(a.mask_in + ((size_t)smp * R + y0) * C * (CO / 4)),
                   mbuf + (par * BPU + bb) * (G::MASK_B / 4), G::MASK_B, 3 + bb, wid, lane);
       }
@@ -323,6 +331,12 @@ __global__ __launch_bounds__(kThreads, 1) void conv_a_kernel(ConvAArgs a) {
           for (int e = 0; e < 4; ++e)
 #pragma unroll
             for (int t = 0; t < PT; ++t) acc[t] = mfma(w[bk * 4 + e], xv[bk & 1][t][e], acc[t]);
+          // BR = 2: nothing moves across a block's end.  Left free at PT = 4, the scheduler hoists
+          // activation reads until <64, 64, 1, 1, 32, 32, 2> spills 22 VGPRs (weights, DMA offsets),
+          // reloaded in the unit loop behind a vmcnt(0) that also waits for the next unit's DMA;
+          // pinned, the 32 x 32 kernels with CI >= 32 take 157-230 VGPRs.  (BR = 4 keeps the code it was
+          // measured with: there pinning was no faster, see above.)
+          if constexpr (BR != 4) __builtin_amdgcn_sched_barrier(0);
         }
       }
     }
@@ -347,11 +361,11 @@ __global__ __launch_bounds__(kThreads, 1) void conv_a_kernel(ConvAArgs a) {
       // issues the same NST buffer stores: a wave with no output (s = 1, or no band) stores
       // through empty resources (dropped), so the next unit's counted wait holds in every wave.
       const bool out = s == 0 && gb < nbands;
-      const int smp = gb / NB, y0 = (gb % NB) * 4;
+      const int smp = gb / NB, y0 = (gb % NB) * BR;
       const size_t bandpos = out ? ((size_t)smp * R + y0) * C : 0;
-      const auto ry = rsrc_over(a.y + bandpos * PO, out ? 4 * C * PO * 4 : 0);
+      const auto ry = rsrc_over(a.y + bandpos * PO, out ? BR * C * PO * 4 : 0);
       const auto rm = rsrc_over(a.mask_out ? a.mask_out + bandpos * (CO / 4) : nullptr,
-                                out && a.mask_out ? 4 * C * (CO / 4) : 0);
+                                out && a.mask_out ? BR * C * (CO / 4) : 0);
       const lds_u8* mk = reinterpret_cast<const lds_u8*>(as_lds(mbuf)) + ((it & 1) * BPU + bslot) * G::MASK_B;
 #pragma unroll
       for (int t = 0; t < PT; ++t) {
@@ -388,7 +402,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_a_kernel(ConvAArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------
-// conv_w_kernel: weight and bias gradient partials per chunk of kChunkBands bands.
+// conv_w_kernel: weight and bias gradient partials per chunk of chunk_bands<BR> bands.
 //   dY [n][R][C][PD] (PD = CO + 4), X [n][R][C][PI]; partial [chunk][WSZ] floats.  An
 //   iteration takes BPI bands (one LDS buffer: their X images, then their dY rows), the next
 //   iteration's bands DMA'd into the other buffer meanwhile.  The band's k-steps (4 positions
@@ -409,20 +423,23 @@ struct ConvWArgs {
   int n;
 };
 
-template <int CI, int CO, int R, int C>
+template <int CI, int CO, int R, int C, int BR>
 struct ConvWGeom {
   static constexpr int PI = Pitch<CI>::v, PD = Pitch<CO>::v, MT = CO / 16, WPM = 8 / MT;
-  static constexpr int RP = C + 2, NB = R / 4, KS = C;  // k-steps (4 positions each) per band
+  static constexpr int RP = C + 2, NB = R / BR, KS = BR * C / 4;  // k-steps (4 positions each) per band
+  static constexpr int CHUNK = chunk_bands<BR>;         // bands per partial
   static constexpr int BPI = CI == 4 ? 4 : 1;           // bands per iteration (one LDS buffer)
-  static constexpr int XB_F = 6 * RP * PI, DB_F = 4 * C * PD, BUF_F = BPI * (XB_F + DB_F);
+  static constexpr int XB_F = (BR + 2) * RP * PI, DB_F = BR * C * PD, BUF_F = BPI * (XB_F + DB_F);
   static constexpr int QW = CI == 4 ? 1 : (CI / 16) / WPM;   // input channels per lane per tap
   static constexpr int NTW = CI == 4 ? 2 : 9 * QW;           // column tiles per wave
   static constexpr int NT_ALL = CI == 4 ? 2 : 9 * (CI / 16); // column tiles per row tile
   static constexpr int WSZ = MT * NT_ALL * 256 + CO;         // partial floats per chunk
   static constexpr int LDS = 2 * BUF_F * 4 + 64;
   static_assert(CI == 4 ? WPM == 4 : (CI / 16) % WPM == 0, "wave split");
-  static_assert(kChunkBands % BPI == 0, "whole iterations per chunk");
+  static_assert(R % BR == 0 && C % 4 == 0, "bands of BR rows, k-steps of 4 positions of one row");
+  static_assert(CHUNK % BPI == 0, "whole iterations per chunk");
   static_assert(CI != 4 || 8 * 2 * 256 <= BPI * DB_F, "the k groups' partial tiles fit the dY images");
+  static_assert(LDS <= 160 * 1024, "the CU's LDS");
 };
 
 // Input channel of column j of the wave's tile qq (CI >= 32, wave half h); for CI == 4 the
@@ -432,11 +449,11 @@ __host__ __device__ constexpr int col_ci(int j, int h, int qq) {
   return CI == 64 ? 8 * (j >> 1) + 2 * (j & 1) + 4 * h + qq : 8 * (j >> 2) + (j & 3) + 4 * h;
 }
 
-template <int CI, int CO, int R, int C>
+template <int CI, int CO, int R, int C, int BR>
 __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
-  using G = ConvWGeom<CI, CO, R, C>;
+  using G = ConvWGeom<CI, CO, R, C, BR>;
   constexpr int PI = G::PI, PD = G::PD, MT = G::MT, RP = G::RP, NB = G::NB, QW = G::QW, NTW = G::NTW;
-  constexpr int BPI = G::BPI, KS = G::KS;
+  constexpr int BPI = G::BPI, KS = G::KS, CHUNK = G::CHUNK;  // (chunk_bands<BR>)
   extern __shared__ f4 smem4[];
   float* smem = reinterpret_cast<float*>(smem4);
   int* slot = reinterpret_cast<int*>(smem + 2 * G::BUF_F);
@@ -444,7 +461,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
   const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int m = wid % MT, h = wid / MT;  // CI == 4: h is the k group
   const int j = lane & 15, g = lane >> 4;
-  const int nbands = a.n * NB, nchunks = (nbands + kChunkBands - 1) / kChunkBands;
+  const int nbands = a.n * NB, nchunks = (nbands + CHUNK - 1) / CHUNK;
   const bool has_bias = CI == 4 ? false : h == 0;  // (CI == 4: the bias is column 27)
 
   // this lane's column offsets within a position (word units)
@@ -471,10 +488,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
     float* b0 = smem + par * G::BUF_F;
 #pragma unroll
     for (int bb = 0; bb < BPI; ++bb) {
-      const int gb = ch * kChunkBands + ib + bb;
+      const int gb = ch * CHUNK + ib + bb;
       if (gb >= nbands) break;
-      load_band<CI, R, C>(a.x, b0 + bb * G::XB_F, gb, bb * 3, wid, lane);
-      const int smp = gb / NB, y0 = (gb % NB) * 4;
+      load_band<CI, R, C, BR>(a.x, b0 + bb * G::XB_F, gb, bb * 3, wid, lane);
+      const int smp = gb / NB, y0 = (gb % NB) * BR;
       dma_range(a.dy + ((size_t)smp * R + y0) * C * PD, b0 + BPI * G::XB_F + bb * G::DB_F, G::DB_F * 4, bb * 3 + 5, wid,
                 lane);
     }
@@ -494,13 +511,13 @@ __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
     for (int t = 0; t < NTW; ++t) acc[t] = f4{0.f, 0.f, 0.f, 0.f};
     accb = f4{0.f, 0.f, 0.f, 0.f};
     int drawn = 0;  // the chunk after next (tid 0), stored to slot[2] once this chunk's k-steps are done
-    for (int i = 0; i < kChunkBands; i += BPI, ++it) {
+    for (int i = 0; i < CHUNK; i += BPI, ++it) {
       const float* xi0 = smem + (it & 1) * G::BUF_F;
       const float* di0 = xi0 + BPI * G::XB_F;
       wait_dma();
       __syncthreads();
       // next iteration: this chunk's next bands, or the first of the next chunk (drawn ahead)
-      if (i + BPI < kChunkBands) {
+      if (i + BPI < CHUNK) {
         issue(chunk, i + BPI, (it + 1) & 1);
       } else {
         // drawn before the DMA goes out (the compiler's wait for the atomic, vmcnt(0), would
@@ -510,7 +527,7 @@ __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
       }
 #pragma unroll
       for (int bb = 0; bb < BPI; ++bb) {
-        if (chunk * kChunkBands + i + bb >= nbands) break;  // (uniform)
+        if (chunk * CHUNK + i + bb >= nbands) break;  // (uniform)
         const float* xi = xi0 + bb * G::XB_F;
         const float* di = di0 + bb * G::DB_F;
 #pragma unroll
@@ -585,10 +602,10 @@ __global__ __launch_bounds__(kThreads, 1) void conv_w_kernel(ConvWArgs a) {
 // order: workgroup = 64 consecutive partial elements; its 4 waves take the chunks k = 4 i + w,
 // each into 8 accumulators by (i mod 8) (8 loads in flight), which are added in order, then the
 // 4 waves' sums in order (deterministic; the association is fixed by nchunks alone).
-template <int CI, int CO, int R, int C>
+template <int CI, int CO, int R, int C, int BR>
 __global__ __launch_bounds__(256) void conv_w_reduce_kernel(const float* __restrict__ partial, int nchunks, int ci_real,
                                                             float* __restrict__ dw, float* __restrict__ db) {
-  using G = ConvWGeom<CI, CO, R, C>;
+  using G = ConvWGeom<CI, CO, R, C, BR>;
   __shared__ float wsum[4][64];
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
   const int e = blockIdx.x * 64 + l;
@@ -711,6 +728,23 @@ __global__ __launch_bounds__(256) void pool20_kernel(const float* __restrict__ a
   feat[smp * 1024 + co * 16 + cell] = sum / 25.f;
 }
 
+// And for R = C = 32 (windows of 8 x 8): 64 loads in flight, the same row-major sum order
+// (0.482 -> 0.320 ms at 6,400 samples against pool_kernel, profiles/train_conv32_passes_*.log).
+__global__ __launch_bounds__(256) void pool32_kernel(const float* __restrict__ a3, int n, float* __restrict__ feat) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= (int64_t)n * 1024) return;
+  const int co = e & 63, cell = (e >> 6) & 15;
+  const int64_t smp = e >> 10;
+  const float* s = a3 + (smp * 1024 + (cell >> 2) * 8 * 32 + (cell & 3) * 8) * 68 + co;
+  float v[64];
+#pragma unroll
+  for (int i = 0; i < 64; ++i) v[i] = s[((i / 8) * 32 + i % 8) * 68];
+  float sum = 0.f;
+#pragma unroll
+  for (int i = 0; i < 64; ++i) sum += v[i];
+  feat[smp * 1024 + co * 16 + cell] = sum / 64.f;
+}
+
 // d3 [n][R][C][68] = (a3 > 0) * (adaptive_avg_pool2d's input gradient of dfeat [n][1024]), the
 // mask from conv3's forward bits m3 [n][R][C][16] (uint8 per 4 channels).  One workgroup per
 // sample: the sample's 1,024 pooled gradients, each divided by its window's area, go to LDS
@@ -785,34 +819,45 @@ int tc_workgroups() {
   return n_cu;
 }
 
-template <int CI, int CO, int S, int MODE>
+// The supported grids and their band heights (the geometry notes at the top of the file).
+#define HEIST_TC_GRIDS(X) X(20, 20, 4) X(32, 32, 2)
+
+template <int CI, int CO, int S, int MODE, int R, int C, int BR>
 static hipError_t launch_a(const tc::ConvAArgs& a, hipStream_t st) {
-  using G = tc::ConvAGeom<CI, CO, S, MODE, 20, 20>;
+  using G = tc::ConvAGeom<CI, CO, S, MODE, R, C, BR>;
   static bool attr = false;
   if (!attr) {
-    hipError_t e = set_lds(&tc::conv_a_kernel<CI, CO, S, MODE, 20, 20>, G::LDS);
+    hipError_t e = set_lds(&tc::conv_a_kernel<CI, CO, S, MODE, R, C, BR>, G::LDS);
     if (e != hipSuccess) return e;
     attr = true;
   }
-  hipLaunchKernelGGL((tc::conv_a_kernel<CI, CO, S, MODE, 20, 20>), dim3(tc_workgroups()), dim3(tc::kThreads), G::LDS,
+  hipLaunchKernelGGL((tc::conv_a_kernel<CI, CO, S, MODE, R, C, BR>), dim3(tc_workgroups()), dim3(tc::kThreads), G::LDS,
                      st, a);
   return hipGetLastError();
+}
+
+template <int R, int C, int BR>
+static hipError_t launch_a_layer(int layer, int mode, const tc::ConvAArgs& a, hipStream_t st) {
+  if (mode == 0) {
+    if (layer == 1) return launch_a<4, 32, 1, 0, R, C, BR>(a, st);
+    if (layer == 2) return launch_a<32, 64, 1, 0, R, C, BR>(a, st);
+    if (layer == 3) return launch_a<64, 64, 1, 0, R, C, BR>(a, st);
+  } else {
+    if (layer == 3) return launch_a<64, 64, 1, 1, R, C, BR>(a, st);
+    if (layer == 2) return launch_a<64, 32, 2, 1, R, C, BR>(a, st);
+  }
+  return hipErrorInvalidValue;
 }
 
 // layer: 1 = conv1 (3 -> 32), 2 = conv2 (32 -> 64), 3 = conv3 (64 -> 64); mode 0 forward, 1 data
 // gradient (layers 2, 3: input = the gradient at the layer's output, 64 channels)
 hipError_t launch_train_conv(int layer, int mode, const float* x, int n, int R, int C, const float* frag,
                              const float* bias, uint8_t* mask_bits, float* y, int* queue, hipStream_t st) {
-  if (R != 20 || C != 20) return hipErrorInvalidValue;
   const tc::ConvAArgs a{x, frag, bias, mode == 1 ? mask_bits : nullptr, mode == 0 ? mask_bits : nullptr, y, queue, n};
-  if (mode == 0) {
-    if (layer == 1) return launch_a<4, 32, 1, 0>(a, st);
-    if (layer == 2) return launch_a<32, 64, 1, 0>(a, st);
-    if (layer == 3) return launch_a<64, 64, 1, 0>(a, st);
-  } else {
-    if (layer == 3) return launch_a<64, 64, 1, 1>(a, st);
-    if (layer == 2) return launch_a<64, 32, 2, 1>(a, st);
-  }
+#define X(R_, C_, BR_) \
+  if (R == R_ && C == C_) return launch_a_layer<R_, C_, BR_>(layer, mode, a, st);
+  HEIST_TC_GRIDS(X)
+#undef X
   return hipErrorInvalidValue;
 }
 
@@ -833,42 +878,68 @@ hipError_t launch_train_conv_pack(int layer, int mode, const float* w, float* fr
   return hipGetLastError();
 }
 
-template <int CI, int CO>
+template <int CI, int CO, int R, int C, int BR>
 static hipError_t launch_w(const float* dy, const float* x, int n, float* partial, float* dw, float* db, int* queue,
                            int ci_real, hipStream_t st) {
-  using G = tc::ConvWGeom<CI, CO, 20, 20>;
+  using G = tc::ConvWGeom<CI, CO, R, C, BR>;
   static bool attr = false;
   if (!attr) {
-    hipError_t e = set_lds(&tc::conv_w_kernel<CI, CO, 20, 20>, G::LDS);
+    hipError_t e = set_lds(&tc::conv_w_kernel<CI, CO, R, C, BR>, G::LDS);
     if (e != hipSuccess) return e;
     attr = true;
   }
   const tc::ConvWArgs a{dy, x, partial, queue, n};
-  hipLaunchKernelGGL((tc::conv_w_kernel<CI, CO, 20, 20>), dim3(tc_workgroups()), dim3(tc::kThreads), G::LDS, st, a);
-  const int nchunks = (n * G::NB + tc::kChunkBands - 1) / tc::kChunkBands;
-  hipLaunchKernelGGL((tc::conv_w_reduce_kernel<CI, CO, 20, 20>), dim3((G::WSZ + 63) / 64), dim3(256), 0, st, partial,
+  hipLaunchKernelGGL((tc::conv_w_kernel<CI, CO, R, C, BR>), dim3(tc_workgroups()), dim3(tc::kThreads), G::LDS, st, a);
+  const int nchunks = (n * G::NB + G::CHUNK - 1) / G::CHUNK;
+  hipLaunchKernelGGL((tc::conv_w_reduce_kernel<CI, CO, R, C, BR>), dim3((G::WSZ + 63) / 64), dim3(256), 0, st, partial,
                      nchunks, ci_real, dw, db);
   return hipGetLastError();
 }
 
+// one partial of WSZ floats per chunk of ConvWGeom::CHUNK bands, as conv_w_kernel counts them
+template <int R, int C, int BR>
+static int64_t partial_floats(int layer, int n) {
+  using G1 = tc::ConvWGeom<4, 32, R, C, BR>;
+  const int64_t nchunks = ((int64_t)n * G1::NB + G1::CHUNK - 1) / G1::CHUNK;
+  if (layer == 1) return nchunks * G1::WSZ;
+  if (layer == 2) return nchunks * tc::ConvWGeom<32, 64, R, C, BR>::WSZ;
+  if (layer == 3) return nchunks * tc::ConvWGeom<64, 64, R, C, BR>::WSZ;
+  return -1;
+}
+
 int64_t train_conv_partial_floats(int layer, int n, int R, int C) {
-  if (R != 20 || C != 20 || n < 0) return -1;
-  const int64_t nchunks = ((int64_t)n * 5 + tc::kChunkBands - 1) / tc::kChunkBands;
-  int wsz = 0;
-  if (layer == 1) wsz = tc::ConvWGeom<4, 32, 20, 20>::WSZ;
-  else if (layer == 2) wsz = tc::ConvWGeom<32, 64, 20, 20>::WSZ;
-  else if (layer == 3) wsz = tc::ConvWGeom<64, 64, 20, 20>::WSZ;
-  else return -1;
-  return nchunks * wsz;
+  if (n < 0) return -1;
+#define X(R_, C_, BR_) \
+  if (R == R_ && C == C_) return partial_floats<R_, C_, BR_>(layer, n);
+  HEIST_TC_GRIDS(X)
+#undef X
+  return -1;
+}
+
+template <int R, int C, int BR>
+static hipError_t launch_w_layer(int layer, const float* dy, const float* x, int n, float* partial, float* dw,
+                                 float* db, int* queue, hipStream_t st) {
+  if (layer == 1) return launch_w<4, 32, R, C, BR>(dy, x, n, partial, dw, db, queue, 3, st);
+  if (layer == 2) return launch_w<32, 64, R, C, BR>(dy, x, n, partial, dw, db, queue, 32, st);
+  if (layer == 3) return launch_w<64, 64, R, C, BR>(dy, x, n, partial, dw, db, queue, 64, st);
+  return hipErrorInvalidValue;
 }
 
 hipError_t launch_train_conv_wgrad(int layer, const float* dy, const float* x, int n, int R, int C, float* partial,
                                    float* dw, float* db, int* queue, hipStream_t st) {
-  if (R != 20 || C != 20) return hipErrorInvalidValue;
-  if (layer == 1) return launch_w<4, 32>(dy, x, n, partial, dw, db, queue, 3, st);
-  if (layer == 2) return launch_w<32, 64>(dy, x, n, partial, dw, db, queue, 32, st);
-  if (layer == 3) return launch_w<64, 64>(dy, x, n, partial, dw, db, queue, 64, st);
+#define X(R_, C_, BR_) \
+  if (R == R_ && C == C_) return launch_w_layer<R_, C_, BR_>(layer, dy, x, n, partial, dw, db, queue, st);
+  HEIST_TC_GRIDS(X)
+#undef X
   return hipErrorInvalidValue;
+}
+
+bool train_conv_grid_supported(int R, int C) {
+#define X(R_, C_, BR_) \
+  if (R == R_ && C == C_) return true;
+  HEIST_TC_GRIDS(X)
+#undef X
+  return false;
 }
 
 hipError_t launch_obs_nhwc4(const float* obs, int n, int R, int C, const int64_t* strides, float* x4, hipStream_t st) {
@@ -883,6 +954,10 @@ hipError_t launch_train_pool(const float* a3, int n, int R, int C, float* feat, 
   const int64_t total = (int64_t)n * 1024;
   if (R == 20 && C == 20) {
     hipLaunchKernelGGL(tc::pool20_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a3, n, feat);
+    return hipGetLastError();
+  }
+  if (R == 32 && C == 32) {
+    hipLaunchKernelGGL(tc::pool32_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a3, n, feat);
     return hipGetLastError();
   }
   hipLaunchKernelGGL(tc::pool_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, a3, n, R, C, feat);

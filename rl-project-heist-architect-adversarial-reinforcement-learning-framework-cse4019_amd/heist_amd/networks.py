@@ -182,7 +182,8 @@ def _mlp_head(seq: nn.Sequential, x: torch.Tensor) -> torch.Tensor:
 
 class _BackboneMFMA32(torch.autograd.Function):
     """SolverNetwork's conv stack (networks.py:93-100) forward and backward on the hand-written
-    fp32-MFMA kernels (csrc/heist_train_conv.hip, heist_train_* in include/heist.h): conv1-3
+    fp32-MFMA kernels (csrc/heist_train_conv.hip, heist_train_* in include/heist.h; 20 x 20 and
+    32 x 32 grids, R and C are passed through): conv1-3
     with bias + ReLU fused in their epilogues (which also write each ReLU mask as bits), the
     4x4 adaptive pool; backward the pool's gradient with conv3's mask, the data gradients of
     conv3 and conv2 with the masks of their inputs fused, and the weight + bias gradients of all
@@ -298,8 +299,10 @@ class SolverNetwork(nn.Module):  # networks.py:13-131
                 and not torch.is_autocast_enabled("cuda") and self.conv3.out_channels == 64
                 and tuple(self.pool.output_size) == (4, 4))
 
-    #: fp32 on a HIP device at 20 x 20: every conv pass on the hand-written fp32-MFMA kernels
-    #: (_BackboneMFMA32); HEIST_TRAIN_CONV=0 or False here keeps MIOpen (_BackboneF32)
+    #: fp32 on a HIP device at 20 x 20 and 32 x 32 (heist_train_conv_supported): every conv pass
+    #: on the hand-written fp32-MFMA kernels (_BackboneMFMA32), in the update and in the no-grad
+    #: rollout forward; HEIST_TRAIN_CONV=0 or False here keeps MIOpen (_BackboneF32), as every
+    #: other grid size does
     mfma_train = True
 
     def _train_conv_ok(self, state: torch.Tensor) -> bool:

@@ -2,7 +2,9 @@
 size (16,384 samples of 20 x 20): the hand-written fp32-MFMA kernels (heist_train_conv*,
 csrc/heist_train_conv.hip) against MIOpen's (torch.ops.aten.convolution / _backward on
 channels-last tensors), HIP events over `iters` launches each after a clock-settle phase,
-algorithmic TFLOP/s against the 157.3 TF fp32 matrix peak.  Prints one JSON line."""
+algorithmic TFLOP/s against the 157.3 TF fp32 matrix peak.  Prints one JSON line.
+PROBE_R=32 times the 32 x 32 kernels (R = C); PROBE_N sets the sample count, by default the
+one with the 20 x 20 minibatch's positions (16,384 * 400 / R^2: 6,400 at 32 x 32)."""
 import json
 import os
 import sys
@@ -37,8 +39,8 @@ def timed(fn, dev, iters=10, settle_ms=200.0):
 
 def main():
     dev = torch.device("cuda:0")
-    n = int(os.environ.get("PROBE_N", "16384"))
-    R = C = 20
+    R = C = int(os.environ.get("PROBE_R", "20"))
+    n = int(os.environ.get("PROBE_N", str(16384 * 400 // (R * C))))
     torch.manual_seed(0)
     net = SolverNetwork(R, R).to(dev)
     L = nat.lib()
@@ -125,7 +127,7 @@ def main():
         out[name]["miopen_frac"] = fl / ms / 1e9 / PEAK
     tot = sum(v["ms"] for v in out.values())
     tot_mi = sum(v["miopen_ms"] for v in out.values())
-    print(json.dumps({"n": n, "passes": out, "pool_passes": mem_out, "sum_ms": tot, "sum_miopen_ms": tot_mi,
+    print(json.dumps({"n": n, "rows": R, "cols": C, "passes": out, "pool_passes": mem_out, "sum_ms": tot, "sum_miopen_ms": tot_mi,
                       "flop_per_step": 3 * sum(flop.values()) - flop[1]}), flush=True)
 
 
