@@ -2170,10 +2170,13 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(multi_oc
 //     loaded at the end of the previous tick, BEFORE that tick's channel-1 stores: vmcnt
 //     counts loads and stores in issue order, so waiting for a load issued after the stores
 //     would wait for the stores to reach memory;
-//   * one visibility plane for cameras and guards (the cached cones ORed in with ds_or_b32);
+//   * the cameras march into the padded visibility plane, the cached cones are ORed
+//     (ds_or_b32) into a packed guard plane, and channel 1 is the OR of the two quads;
 //     detection reads the solver's byte from the channel-1 quads the observation loads
-//     anyway; a finishing env whose guards stood off their start re-casts from the reset
-//     poses (rare: the reset observation needs the guards at patrol point 0);
+//     anyway; a finishing env whose guards stood off their start clears and restamps the
+//     guard plane alone from the reset poses' cones, staged with the tick's own (the reset
+//     observation needs the guards at patrol point 0; a reset keeps the camera headings, so
+//     the cameras' share stands);
 //   * a camera group the shared fan serves (every live camera's emitter equals the tick's
 //     table entry, no near-tie ray, range 6) marches the table's unique directions from
 //     each camera's tile, one address add per sample: the table holds each sample's tile as
@@ -2249,9 +2252,10 @@ __device__ __noinline__ void ivl_tie_rays(unsigned char* smem, int ray, double h
 // The lean kernel's LDS: the three padded planes (stop map, visibility, sink; the step
 // kernels' geometry, so exact_ray works on them), the tile grid, the patrol paths, the
 // launch's K actions, the LDS-DMA staging of the next tick's HBM data (LeanStage), the
-// cached guards' cone rows [tick parity][rows 0-7 | 8-15][max_guards] x 16 B, and the static
-// position plane (channel 2 with the vault patched) -- or step_multi_body's, if larger, for
-// the envs that take it.
+// cached guards' cone rows [tick parity][rows 0-7 | 8-15][max_guards] x 16 B, the same for
+// their reset pose (patrol point 0), the packed guard plane (R x C bytes at row pitch C: the
+// cones name in-grid tiles only) and the static position plane (channel 2 with the vault
+// patched) -- or step_multi_body's, if larger, for the envs that take it.
 size_t step_multi_lds(const EnvParams& p, int K);
 struct LeanStage {
   uint4 off4[128];  // the fan's unique directions 0 .. 127, samples 1-8 (FanTick::off4)
@@ -2297,6 +2301,8 @@ struct LeanLds {
   uint4* icam;     // interval fans, per camera: start angle, first cut, rays | tile << 16
   int32_t* icim;   //   and 2^52 / ray spacing (rounded; < 2^31)
   uint16_t* cone;
+  uint16_t* rcone;  // the cone rows of the reset pose (patrol point 0, the same heading slot)
+  uint8_t* gpl;     // the guards' share of the visibility plane, packed
   float4* plane2;
 };
 // The lean kernel's plane gap D: the padded (R + 12) x (C + 12) plane in 1024 (up to 20 x 20)
@@ -2320,6 +2326,10 @@ __host__ __device__ inline size_t lean_carve(unsigned char* smem, int R, int C, 
   o += align16(8 * (size_t)(mc > 0 ? mc : 1));
   if (L) L->cone = reinterpret_cast<uint16_t*>(smem + o);
   o += 64 * (size_t)(mg > 0 ? mg : 1);
+  if (L) L->rcone = reinterpret_cast<uint16_t*>(smem + o);
+  o += 64 * (size_t)(mg > 0 ? mg : 1);
+  if (L) L->gpl = smem + o;
+  o += align16((size_t)R * C);
   if (L) L->plane2 = reinterpret_cast<float4*>(smem + o);
   o += 4 * (size_t)R * C;
   return o;
@@ -2497,6 +2507,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   const uint32_t base = (uint32_t)(uintptr_t)smem;  // LDS address of the stop map
   const uint32_t stg_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)L.stg);
   const uint32_t stc_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)L.cone);
+  const uint32_t str_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)L.rcone);
+  const uint32_t gpl_a = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(uintptr_t)L.gpl);
+  static_assert(RC % 16 == 0, "the packed guard plane is cleared in 16-byte words");
   {
     // grid (static observation channel 0) and the padded stop map, as prefetch does
     const uint32_t* g4 = reinterpret_cast<const uint32_t*>(p.grid + (size_t)e * RC);
@@ -2523,8 +2536,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   // HBM data a tick needs -- its shared fan entry (FanTick: the unique directions' sample
   // tiles, n_uniq, n_tie) and its cached guards' cone entries -- comes by LDS-DMA issued a
   // tick ahead: the fan entry once the tick has marched its own (the staging is then free),
-  // a cone entry once the guard's move is known (the pose after the next move; a finishing
-  // env re-issues it for its reset pose; double-buffered by tick parity).  The tick's stores
+  // a cone entry once the guard's move is known (the pose after the next move, and with it
+  // the entry a reset at that tick restamps: patrol point 0 at the same heading slot; a
+  // finishing env re-issues both from its reset pose; double-buffered by tick parity).  So no
+  // tick waits for a global load of its own.  The tick's stores
   // go last, so the next tick's counted wait for the DMA (kStores younger operations)
   // never waits for a store to reach memory.
   auto dma_fan = [&](int k, bool wide) {  // k < K
@@ -2534,17 +2549,20 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     lds_dma16(f->off2 + 2 * lane, stg_a + (uint32_t)offsetof(LeanStage, off2));
     if (lane == 0) lds_dma16(&f->num_rays, stg_a + (uint32_t)offsetof(LeanStage, hdr));
   };
-  // the cone entry (rows 0-15, 32 B) of cached guard g at (idx, slot) into cone staging
-  // `par`: lane mc + g writes at the base it is given minus 16 mc
-  auto dma_cone = [&](int idx, int slot, int par) {
+  // the cone entry (rows 0-15, 32 B) of cached guard g at (idx, slot) into parity `par` of
+  // the cone staging at LDS address `stage`: lane mc + g writes at the base it is given
+  // minus 16 mc
+  auto dma_cone = [&](int idx, int slot, uint32_t stage, int par) {
     if (cached) {
       const uint16_t* src = eb.cones + cone_off((uint32_t)g, (uint32_t)idx, (uint32_t)slot);
-      const uint32_t dst = stc_a + (uint32_t)(par * 32 * mg) - 16u * (uint32_t)mc;
+      const uint32_t dst = stage + (uint32_t)(par * 32 * mg) - 16u * (uint32_t)mc;
       lds_dma16(src, dst);
       lds_dma16(src + 8, dst + 16u * (uint32_t)mg);
     }
   };
-  // the entry of the pose after a move from the guard's current one (idx + step, nslot)
+  // the entry of the pose after a move from the guard's current one (idx + step, nslot), and
+  // the entry of the pose a reset at that tick puts the guard in (patrol point 0, the same
+  // slot: a reset keeps the heading); a guard that does not patrol gets its own entry twice
   auto dma_next_cone = [&](int par) {
     int idx = gd.idx(), slot = gd.hslot();
     if (gd.len() >= 2) {
@@ -2552,7 +2570,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (idx >= gd.len()) idx -= gd.len();
       slot = (int)gd.nslot;
     }
-    dma_cone(idx, slot, par);
+    dma_cone(idx, slot, stc_a, par);
+    if (auto_reset) dma_cone(0, slot, str_a, par);
   };
   if (wid == 0) dma_next_cone(0);
   if (ivl) {  // the interval table into the staging space (LDS-DMA, 16 B per lane per pass)
@@ -2565,20 +2584,25 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   if (NW == 2) __syncthreads();  // both waves' parts of the table in place
 
-  // the cached guards' cone rows (staging parity par) ORed into the plane: lane 15 i + j
-  // takes row j of guard slot 4 pass + i; bit dc + 7 of row dr + 7 is tile (gr + dr, gc + dc);
-  // the aligned dwords a row spans get its bits as 0/1 bytes (ds_or_b32)
+  // the guards' share of the tick's visibility: the packed guard plane cleared and the cached
+  // guards' cone rows (parity par of the staging `rows`) ORed into it: lane 15 i + j takes
+  // row j of guard slot 4 pass + i; bit dc + 7 of row dr + 7 is tile (gr + dr, gc + dc), set
+  // for in-grid tiles only (cones_kernel), so rows and dwords outside the plane carry no bit;
+  // the aligned dwords a row spans get its bits as 0/1 bytes (ds_or_b32).  The cameras' share
+  // stays in the visibility plane, so a reset restamps the cones alone.  One wave's work (in
+  // order on its LDS queue).
   const uint64_t cmask = __ballot(cached);
-  auto stamp_cones = [&](int par) {
+  auto stamp_cones = [&](const uint16_t* rows, int par) {
+    if (lane < RC / 16) reinterpret_cast<uint4*>(L.gpl)[lane] = make_uint4(0u, 0u, 0u, 0u);
     const uint32_t gposv = gd.pos();
     for (int pass = 0; pass * 4 < mg; ++pass) {
       const int i = lane / 15, j = lane - 15 * i;
       const int gs = 4 * pass + i;
       const uint32_t gp = (uint32_t)__shfl((int)gposv, mc + (gs < mg ? gs : 0), 64);
       if (lane < 60 && gs < mg && ((cmask >> (mc + gs)) & 1u)) {
-        const uint32_t bits = L.cone[par * 16 * mg + (j >> 3) * 8 * mg + 8 * gs + (j & 7)] & 0x7fffu;
+        const uint32_t bits = rows[par * 16 * mg + (j >> 3) * 8 * mg + 8 * gs + (j & 7)] & 0x7fffu;
         if (bits) {
-          const uint32_t a0 = base + D + OFF0 + (unpack_r((uint16_t)gp) + j - kConeRange) * PC +
+          const uint32_t a0 = gpl_a + (unpack_r((uint16_t)gp) + j - kConeRange) * C_ +
                               (unpack_c((uint16_t)gp) - kConeRange);
           const uint32_t m = bits << (a0 & 3u);
           const uint32_t a = a0 & ~3u;
@@ -2614,11 +2638,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       lds_st(__umul24(skip, (uint32_t)D) + a[u] + D, 1);
     }
   };
-  // this tick's visibility into the cleared plane: every camera marches the shared fan's
-  // unique directions -- from the staging, or (the reset pass, after the next tick's DMA
-  // took the staging) from the table -- with the table's near-tie rays on the exact path,
-  // then the cached cones
-  auto cast_fan = [&](int k, int n_uniq, int n_tie, int par, bool staged, bool staged_wide) {
+  // this tick's visibility: into the cleared plane every camera marches the shared fan's
+  // unique directions from the staging, with the table's near-tie rays on the exact path;
+  // the cached cones go into the guard plane
+  auto cast_fan = [&](int k, int n_uniq, int n_tie, int par, bool staged_wide) {
 #pragma unroll
     for (int z = 0; z < D / 1024; ++z)  // 64 x 16 B per pass: the plane
       reinterpret_cast<uint4*>(vis)[lane + 64 * z] = make_uint4(0u, 0u, 0u, 0u);
@@ -2627,30 +2650,22 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     uint2 o2a = make_uint2(0u, 0u), o2b = o2a;
     if (s.n_cams > 0) {
       const bool want_b = n_uniq > 64;
-      if (staged) {
-        o4a = L.stg->off4[lane];
-        o2a = L.stg->off2[lane];
-        if (want_b && staged_wide) {
-          o4b = L.stg->off4[64 + lane];
-          o2b = L.stg->off2[64 + lane];
-        }
+      o4a = L.stg->off4[lane];
+      o2a = L.stg->off2[lane];
+      if (want_b && staged_wide) {
+        o4b = L.stg->off4[64 + lane];
+        o2b = L.stg->off2[64 + lane];
       }
-      if (!staged || (want_b && !staged_wide)) {  // from the table (rare): waited for here, not after the join
-        if (!staged) {
-          o4a = f->off4[lane];
-          o2a = f->off2[lane];
-        }
-        if (want_b) {
-          o4b = f->off4[64 + lane];
-          o2b = f->off2[64 + lane];
-        }
+      if (want_b && !staged_wide) {  // from the table (rare): waited for here, not after the join
+        o4b = f->off4[64 + lane];
+        o2b = f->off2[64 + lane];
         asm volatile("" ::"v"(__builtin_bit_cast(u32x4_t, o4a)), "v"(__builtin_bit_cast(u32x2_t, o2a)),
                      "v"(__builtin_bit_cast(u32x4_t, o4b)), "v"(__builtin_bit_cast(u32x2_t, o2b)));
       }
     }
     // the tick's fan entry is in registers, the staging free: tick k + 1's entry goes out now,
     // a whole cast ahead of the next tick's wait for it (once the staging reads have returned)
-    if (staged && k + 1 < K) {
+    if (k + 1 < K) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::"v"(__builtin_bit_cast(u32x4_t, o4a)), "v"(__builtin_bit_cast(u32x2_t, o2a)),
                    "v"(__builtin_bit_cast(u32x4_t, o4b)), "v"(__builtin_bit_cast(u32x2_t, o2b))
                    : "memory");
@@ -2668,7 +2683,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (n_tie > 0) lean_tie_rays<D, PC>(smem, f, n_tie, cam_rc, s.n_cams, p.half_deg);
     }
     LEAN_STAMP(2);
-    stamp_cones(par);
+    stamp_cones(L.cone, par);
   };
   // this tick's visibility from the interval table (an env the shared fan does not serve).
   // Ray i of a camera lies i * su angle units past its fixed-point start h0 (the reference's
@@ -2769,16 +2784,25 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (safe) march_at(cu.z >> 16, dj);
     }
     LEAN_STAMP(2);
-    if (wid == 0) stamp_cones(par);
-    wave_join();  // the plane is complete
+    if (wid == 0) stamp_cones(L.cone, par);
+    wave_join();  // the planes are complete
   };
-  auto cast = [&](int k, int n_uniq, int n_tie, int par, bool staged, bool staged_wide) {
+  auto cast = [&](int k, int n_uniq, int n_tie, int par, bool staged_wide) {
     if (ivl) {
       cast_ivl(par);
     } else {  // the shared fan: wave 0's (its staging and DMA are wave 0's)
       wave_join();
-      if (wid == 0) cast_fan(k, n_uniq, n_tie, par, staged, staged_wide);
+      if (wid == 0) cast_fan(k, n_uniq, n_tie, par, staged_wide);
       wave_join();
+    }
+  };
+  // the channel-1 quads this wave stores: the cameras' share | the guards'
+  auto read_v1 = [&](uint32_t (&v1)[QW]) {
+#pragma unroll
+    for (int j = 0; j < QW; ++j) {
+      const int q = lane + 64 * (wid * QW + j), qc = q < N4 ? q : N4 - 1, r = qc / C4;
+      v1[j] = *reinterpret_cast<const uint32_t*>(vis + OFF0 + r * PC + 4 * (qc - r * C4)) |
+              *reinterpret_cast<const uint32_t*>(L.gpl + 4 * qc);
     }
   };
 
@@ -2830,18 +2854,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       if (k + 1 < K && wid == 0) dma_next_cone(par ^ 1);  // tick k + 1's entry if the env still acts then
       LEAN_STAMP(1);  // 1: move, rotation, patrol
       // 3. visibility (environment.py:257-258)
-      cast(k, n_uniq, n_tie, par, true, staged_wide);
+      cast(k, n_uniq, n_tie, par, staged_wide);
       LEAN_STAMP(3);  // 3: the cached guard cones (2: the cameras, inside cast)
     }
-    // (tick k + 1's fan entry went out inside cast_fan; a frozen env keeps its plane and skips it)
+    // (tick k + 1's fan entry went out inside cast_fan; a frozen env keeps its planes and skips it)
     wide = n_uniq > 64;
-    // the plane's channel-1 quads this wave stores (one wave: also the detection test's byte)
+    // the planes' channel-1 quads this wave stores (one wave: also the detection test's byte)
     uint32_t v1[QW];
-#pragma unroll
-    for (int j = 0; j < QW; ++j) {
-      const int q = lane + 64 * (wid * QW + j), qc = q < N4 ? q : N4 - 1, r = qc / C4;
-      v1[j] = *reinterpret_cast<const uint32_t*>(vis + OFF0 + r * PC + 4 * (qc - r * C4));
-    }
+    read_v1(v1);
     int done_now = s.done;
     LEAN_STAMP(4);  // 4: next fan DMA, the channel-1 quads
     if (!frozen) {
@@ -2855,7 +2875,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
         const uint32_t qv = (uint32_t)__builtin_amdgcn_readlane((int)vq, qs & 63);
         seen = ((qv >> (8 * (sol & 3))) & 0xffu) != 0u;
       } else {  // the quad may be the other wave's: the byte itself
-        seen = vis[OFF0 + s.pos_r * PC + s.pos_c] != 0;
+        seen = (vis[OFF0 + s.pos_r * PC + s.pos_c] | L.gpl[s.pos_r * C_ + s.pos_c]) != 0;
       }
       if (seen) {
         s.detected = 1;
@@ -2889,22 +2909,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
         gd.a &= ~0xffu;                        // idx 0
         gd.b = (gd.b & 0xffff0000u) | gd.pos0();  // the patrol start
       }
-      if (cached && wid == 0) {  // the cone of (patrol point 0, this slot), loaded now: only finishing envs pay for it
-        const uint4* rsrc = reinterpret_cast<const uint4*>(eb.cones + cone_off(g, 0, gd.hslot()));
-        const uint4 ra = rsrc[0], rb = rsrc[1];
-        if (moved) {
-          *reinterpret_cast<uint4*>(L.cone + par * 16 * mg + 8 * g) = ra;
-          *reinterpret_cast<uint4*>(L.cone + par * 16 * mg + 8 * mg + 8 * g) = rb;
-        }
-        gd.nslot = rb.w >> 16;
-      }
-      if (moved) {  // the plane again from the reset poses (the staging holds tick k + 1's fan now)
-        cast(k, n_uniq, n_tie, par, false, false);
-#pragma unroll
-        for (int j = 0; j < QW; ++j) {
-          const int q = lane + 64 * (wid * QW + j), qc = q < N4 ? q : N4 - 1, r = qc / C4;
-          v1[j] = *reinterpret_cast<const uint32_t*>(vis + OFF0 + r * PC + 4 * (qc - r * C4));
-        }
+      // the cone of (patrol point 0, this slot) was staged a tick ago with the tick's own: the
+      // slot after the next move from there is its row 15
+      if (cached && wid == 0) gd.nslot = L.rcone[par * 16 * mg + 8 * mg + 8 * g + 7];
+      if (moved) {  // the guard plane again from the reset poses; the cameras' share stands (headings kept)
+        wave_join();  // both waves have read the tick's guard plane
+        if (wid == 0) stamp_cones(L.rcone, par);
+        wave_join();
+        read_v1(v1);
       }
       if (k + 1 < K && wid == 0) dma_next_cone(par ^ 1);  // tick k + 1's entry from the reset pose
     }
