@@ -114,6 +114,41 @@ int heist_step_multi(heist_t h, int K, const int64_t* actions, float* obs_out, f
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,
                  double* guard_heading, heist_stream_t stream);
 
+/* Compact observation records, no reference counterpart as an entry point: a lossless restatement
+ * of get_state_tensor's output (environment.py:305-374) for callers that keep many observations
+ * (the trainer's rollout buffer).  Channel 0 is grid / 5 and constant while a layout stands, channel
+ * 2 is a function of the vault's and the solver's cell, and channel 1 is one bit per cell, so a
+ * record holds the bits and the cell; the grid is kept once per env.
+ * One record is W little-endian uint32 words, W = ceil(R*C / 32) + 1 rounded up to a multiple of 4
+ * (16-byte records): 64 B at 20 x 20, 144 B at 32 x 32, 32 B at 13 x 17 and 10 x 10, 528 B at 64 x 64.
+ *   words 0 .. ceil(R*C/32)-1: visibility; bit i of word j is cell 32 j + i (row-major, r*C + c),
+ *     1 iff channel 1 of the cell is non-zero; bits past R*C are 0
+ *   the next word: pos_r | pos_c << 8, the solver's cell
+ *   the remaining words: 0 (equal observations give byte-equal records)
+ * heist_obs_record_bytes: 4 W, or -1 (heist_last_error) unless 1 <= rows, cols <= 64.
+ * heist_obs_pack: obs [n][3][R][C] float32 (heist_reset / heist_step output, or the [K][N] rows of
+ *   a heist_step_multi launch) -> records [n][W].  The solver's cell is the one cell of channel 2
+ *   above 0.5 (1 - 0.3 d / (R + C) >= 0.7 there, every other cell <= 0); with no such cell the solver
+ *   stands on the vault, whose -1 overwrites its 1 (environment.py:359-360), and the record holds
+ *   (vault_r, vault_c).
+ * heist_obs_expand: obs_out [m][3][R][C] float32, sample i rebuilt from record j = index[i] (int64;
+ *   index == NULL: j = i) of records [n_records][W], bit-identical to the observation the record was
+ *   packed from: channel 0 = (float)grid[rec_env[j]][cell] / 5.0f with grid [n_envs][R][C] int8 as
+ *   heist_export wrote it while the records' layouts stood, channel 1 = bit ? 1.0f : 0.0f, channel
+ *   2 = base + (float)(-0.3 * ((double)d / (double)(R + C))) with base -1 on the vault, else 1 on the
+ *   solver's cell, else 0, and d the Manhattan distance to the vault (environment.py:357-367).
+ *   rec_env [n_records] int32 is each record's env.  It takes no handle: records and the grid
+ *   snapshot stay valid after heist_set_layout changes the env.  A j outside [0, n_records) or an
+ *   env outside [0, n_envs) gives a sample of NaNs.
+ * n, m >= 0 (0: no-op).  16-byte aligned obs / obs_out with R*C a multiple of 4 take the 16-byte
+ * load / store path. */
+int heist_obs_record_bytes(int rows, int cols);
+int heist_obs_pack(const float* obs, int64_t n, int rows, int cols, int vault_r, int vault_c, uint32_t* records,
+                   heist_stream_t stream);
+int heist_obs_expand(const uint32_t* records, int64_t n_records, const int32_t* rec_env, const int64_t* index, int64_t m,
+                     const int8_t* grid, int n_envs, int rows, int cols, int vault_r, int vault_c, float* obs_out,
+                     heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

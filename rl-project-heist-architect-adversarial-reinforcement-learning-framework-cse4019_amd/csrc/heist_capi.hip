@@ -88,6 +88,10 @@ hipError_t launch_rollout_tally(const uint8_t* valid, int32_t* attempts, int A, 
                                 int det, hipStream_t st);
 hipError_t launch_lstm_cell(const float* gx, const float* gh, const float* c, float* h1, float* c1, int H, int n,
                             hipStream_t st);
+int obs_record_words(int R, int C);
+hipError_t launch_obs_pack(const float* obs, int64_t n, int R, int C, int vr, int vc, uint32_t* rec, hipStream_t st);
+hipError_t launch_obs_expand(const uint32_t* rec, int64_t n_rec, const int32_t* rec_env, const int64_t* index, int64_t m,
+                             const int8_t* grid, int n_envs, int R, int C, int vr, int vc, float* out, hipStream_t st);
 hipError_t launch_adv_moments(const float* x, int64_t n, int phase, double* acc, hipStream_t st);
 hipError_t launch_adv_apply(float* x, int64_t n, const double* acc, float eps, hipStream_t st);
 hipError_t launch_ppo_loss(const float* logits, const float* values, const int64_t* actions, const float* old_logp,
@@ -681,6 +685,43 @@ int heist_lstm_cell(const float* gates_x, const float* gates_h, const float* c, 
   HEIST_REQUIRE(gates_x && gates_h && c && h_out && c_out, "heist_lstm_cell: null pointer");
   return check_hip(heist::launch_lstm_cell(gates_x, gates_h, c, h_out, c_out, hidden, n, (hipStream_t)stream),
                    "heist_lstm_cell");
+}
+
+int heist_obs_record_bytes(int rows, int cols) {
+  if (!(rows >= 1 && cols >= 1 && rows <= heist::kMaxDim && cols <= heist::kMaxDim)) {
+    fail(HEIST_EINVAL, "heist_obs_record_bytes: need 1 <= rows, cols <= 64");
+    return -1;
+  }
+  return 4 * heist::obs_record_words(rows, cols);
+}
+
+int heist_obs_pack(const float* obs, int64_t n, int rows, int cols, int vault_r, int vault_c, uint32_t* records,
+                   heist_stream_t stream) {
+  HEIST_REQUIRE(rows >= 1 && cols >= 1 && rows <= heist::kMaxDim && cols <= heist::kMaxDim,
+                "heist_obs_pack: need 1 <= rows, cols <= 64");
+  HEIST_REQUIRE(vault_r >= 0 && vault_r < rows && vault_c >= 0 && vault_c < cols, "heist_obs_pack: vault outside the grid");
+  HEIST_REQUIRE(n >= 0, "heist_obs_pack: negative n");
+  if (n == 0) return 0;
+  HEIST_REQUIRE(obs && records, "heist_obs_pack: null pointer");
+  HEIST_REQUIRE(((uintptr_t)obs & 3) == 0 && ((uintptr_t)records & 3) == 0, "heist_obs_pack: 4-byte alignment");
+  return check_hip(heist::launch_obs_pack(obs, n, rows, cols, vault_r, vault_c, records, (hipStream_t)stream),
+                   "heist_obs_pack");
+}
+
+int heist_obs_expand(const uint32_t* records, int64_t n_records, const int32_t* rec_env, const int64_t* index, int64_t m,
+                     const int8_t* grid, int n_envs, int rows, int cols, int vault_r, int vault_c, float* obs_out,
+                     heist_stream_t stream) {
+  HEIST_REQUIRE(rows >= 1 && cols >= 1 && rows <= heist::kMaxDim && cols <= heist::kMaxDim,
+                "heist_obs_expand: need 1 <= rows, cols <= 64");
+  HEIST_REQUIRE(vault_r >= 0 && vault_r < rows && vault_c >= 0 && vault_c < cols,
+                "heist_obs_expand: vault outside the grid");
+  HEIST_REQUIRE(m >= 0 && n_records >= 0 && n_envs >= 0, "heist_obs_expand: negative size");
+  if (m == 0) return 0;
+  HEIST_REQUIRE(records && rec_env && grid && obs_out, "heist_obs_expand: null pointer");
+  HEIST_REQUIRE(((uintptr_t)obs_out & 3) == 0 && ((uintptr_t)records & 3) == 0, "heist_obs_expand: 4-byte alignment");
+  return check_hip(heist::launch_obs_expand(records, n_records, rec_env, index, m, grid, n_envs, rows, cols, vault_r,
+                                            vault_c, obs_out, (hipStream_t)stream),
+                   "heist_obs_expand");
 }
 
 int heist_gae(const float* rewards, const float* values, const uint8_t* dones, const float* last_value, int T, int n,

@@ -9,7 +9,7 @@ gradients of every optimizer step are averaged with ONE flat all-reduce.
 """
 from collections import deque
 from dataclasses import dataclass
-from typing import Dict, Optional
+from typing import Dict, Optional, Union
 
 import numpy as np
 import torch
@@ -17,6 +17,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from ..networks import SolverNetwork
+from ..obs_compact import CompactObs
 from .. import dist_utils
 from ..dist_utils import allreduce_grads  # noqa: F401  (re-exported: the reference-facing name)
 from ..ppo import compute_gae, normalize_advantages, ppo_loss
@@ -26,7 +27,7 @@ from ..utils import DEVICE
 @dataclass
 class Rollout:
     """[T, N] time-major rollout of the batched environment."""
-    obs: torch.Tensor       # [T, N, 3, R, C] float32
+    obs: Union[torch.Tensor, CompactObs]  # [T, N, 3, R, C] float32, or its records (obs_storage="compact")
     actions: torch.Tensor   # [T, N] int64
     logp: torch.Tensor      # [T, N] float32
     values: torch.Tensor    # [T, N] float32
@@ -181,7 +182,8 @@ class SolverAgent:  # agents/solver.py:18-259
                 if start < n:
                     b = idx[start:start + bs]
                     w = int(b.numel())
-                    x = states[b]
+                    # records are expanded per minibatch (one launch): the same bits as the gather
+                    x = states.expand(b) if isinstance(states, CompactObs) else states[b]
                     # MIOpen's convolutions want channels-last; the fp32-MFMA backbone reads the
                     # gathered rows with their own strides (one pass to NHWC4 either way)
                     if x.is_cuda and not (self.update_precision == "fp32" and self.network._train_conv_ok(x)):
@@ -280,7 +282,8 @@ class SolverAgent:  # agents/solver.py:18-259
         adv, ret = self.rollout_advantages(ro)
         sel = None if ro.mask is None else ro.mask.reshape(1, N).expand(T, N).reshape(-1)
         flat = lambda x: x.reshape(T * N, *x.shape[2:])  # noqa: E731
-        states, actions, old_logp, adv, ret = flat(ro.obs), flat(ro.actions), flat(ro.logp), flat(adv), flat(ret)
+        states = ro.obs.flat() if isinstance(ro.obs, CompactObs) else flat(ro.obs)
+        actions, old_logp, adv, ret = flat(ro.actions), flat(ro.logp), flat(adv), flat(ret)
         if sel is not None:
             states, actions, old_logp, adv, ret = (x[sel] for x in (states, actions, old_logp, adv, ret))
         n = adv.shape[0]

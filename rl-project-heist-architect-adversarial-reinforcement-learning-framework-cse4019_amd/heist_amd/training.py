@@ -46,6 +46,7 @@ from . import dist_utils
 from .agents.architect import ArchitectAgent
 from .agents.solver import Rollout, SolverAgent
 from .environment import EnvironmentConfig, HeistEnvironment, accept_layout
+from .obs_compact import CompactObs, record_words
 from .rewards import RewardCalculator
 from .utils import DEVICE
 from .vec_env import STATUS_CODES, HeistEnv
@@ -156,7 +157,7 @@ class AdversarialTrainer:  # training.py:115-790
                  rollout_len: Optional[int] = None, minibatch: int = 4096, device=None, max_budget: Optional[int] = None,
                  seed: Optional[int] = None, update_precision: str = "fp32", rollout_precision: str = "fp32",
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
-                 solver_cadence: str = "rollout"):
+                 solver_cadence: str = "rollout", obs_storage: str = "full"):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -183,6 +184,12 @@ class AdversarialTrainer:  # training.py:115-790
         if solver_cadence not in ("rollout", "layout_batch"):
             raise ValueError("solver_cadence must be 'rollout' or 'layout_batch'")
         self.solver_cadence = solver_cadence
+        # "full": the rollout keeps every observation as [3, R, C] float32; "compact": as records
+        # (obs_compact.CompactObs: 64 B at 20 x 20 plus one grid per env), expanded per minibatch in
+        # the update -- the same bits, 75-85x less rollout memory
+        if obs_storage not in ("full", "compact"):
+            raise ValueError("obs_storage must be 'full' or 'compact'")
+        self.obs_storage = obs_storage
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -353,6 +360,8 @@ class AdversarialTrainer:  # training.py:115-790
         env.obs), so no per-tick copy.  last_value = V(s_T) under the carried LSTM state
         (zeroed where an attempt just ended; those columns are masked by done anyway)."""
         env, n, d = self.env, self.n_envs, self.device
+        if self.obs_storage == "compact":
+            return self._rollout_compact(T)
         obs_buf = torch.empty((T, n) + tuple(env.obs.shape[1:]), dtype=torch.float32, device=d)
         act_buf = torch.empty((T, n), dtype=torch.int64, device=d)
         lp_buf = torch.empty((T, n), dtype=torch.float32, device=d)
@@ -375,6 +384,35 @@ class AdversarialTrainer:  # training.py:115-790
         return Rollout(obs_buf, act_buf, lp_buf, v_buf, r_buf, d_buf, mask=self.b_valid.clone(),
                        last_value=last_value)
 
+    def _rollout_compact(self, T: int) -> Rollout:
+        """_rollout with obs_storage="compact": the policy reads env.obs, which heist_step
+        rewrites in place each tick, and the rollout keeps tick t's observation as records
+        (heist_obs_pack into rec_buf[t]) under one grid snapshot taken at the start -- layouts
+        only change between rollouts.  Same launches otherwise, so the same actions and rewards."""
+        env, n, d = self.env, self.n_envs, self.device
+        grid = env.grid_snapshot()
+        rec_buf = torch.empty((T, n, record_words(env.rows, env.cols)), dtype=torch.int32, device=d)
+        act_buf = torch.empty((T, n), dtype=torch.int64, device=d)
+        lp_buf = torch.empty((T, n), dtype=torch.float32, device=d)
+        v_buf = torch.empty((T, n), dtype=torch.float32, device=d)
+        r_buf = torch.empty((T, n), dtype=torch.float32, device=d)
+        d_buf = torch.empty((T, n), dtype=torch.uint8, device=d)
+        A = self.solver_episodes
+        vault, det = STATUS_CODES["vault_reached"], STATUS_CODES["detected"]
+        for t in range(T):
+            a, lp, v, (self.h, self.c) = self.solver.act(env.obs, (self.h, self.c))
+            act_buf[t], lp_buf[t], v_buf[t] = a, lp, v
+            env.pack_obs(env.obs, out=rec_buf[t])
+            _, rew, done, status = env.step(a)
+            r_buf[t] = rew
+            d_buf[t] = done.to(torch.uint8)
+            if self._trace is not None:
+                self._trace.append((a.clone(), env.reward64.clone(), done.clone(), status.clone()))
+            self._tally(done, status, A, vault, det)
+        last_value = self.solver.value(env.obs, (self.h, self.c))
+        return Rollout(CompactObs.of_env(env, rec_buf, grid), act_buf, lp_buf, v_buf, r_buf, d_buf,
+                       mask=self.b_valid.clone(), last_value=last_value)
+
     @torch.no_grad()
     def _rollout_layout_batch(self) -> Tuple[Rollout, torch.Tensor]:
         """Play until every valid env has finished its layout's A attempts (at most
@@ -387,23 +425,28 @@ class AdversarialTrainer:  # training.py:115-790
         T_max = A * self.config.max_steps
         vault, det = STATUS_CODES["vault_reached"], STATUS_CODES["detected"]
         bufs = {k: [] for k in ("obs", "act", "lp", "v", "r", "d", "sel")}
-        obs = env.obs.clone()
+        compact = self.obs_storage == "compact"
+        grid = env.grid_snapshot() if compact else None  # the layouts stand until the rollout ends
+        obs = env.obs if compact else env.obs.clone()  # compact: packed before heist_step rewrites env.obs
         t = 0
         while t < T_max:
             counting = self.b_valid & (self.b_attempts < A)
             if t % 16 == 0 and not bool(counting.any()):
                 break
             a, lp, v, (self.h, self.c) = self.solver.act(obs, (self.h, self.c))
+            kept = env.pack_obs(obs) if compact else obs
             nxt, rew, done, status = env.step(a)
-            for k, x in (("obs", obs), ("act", a), ("lp", lp), ("v", v), ("r", rew.clone()),
+            for k, x in (("obs", kept), ("act", a), ("lp", lp), ("v", v), ("r", rew.clone()),
                          ("d", done.to(torch.uint8)), ("sel", counting)):
                 bufs[k].append(x)
             if self._trace is not None:
                 self._trace.append((a.clone(), env.reward64.clone(), done.clone(), status.clone()))
             self._tally(done, status, A, vault, det)  # (counting as above; solver.reset() per attempt)
-            obs = nxt.clone()
+            obs = nxt if compact else nxt.clone()
             t += 1
         st = {k: torch.stack(v) for k, v in bufs.items()}
+        if compact:
+            st["obs"] = CompactObs.of_env(env, st["obs"], grid)
         ro = Rollout(st["obs"], st["act"], st["lp"], st["v"], st["r"], st["d"], mask=self.b_valid.clone(),
                      last_value=None)
         return ro, st["sel"]

@@ -314,6 +314,40 @@ class HeistEnv:
             out["grid"] = gr
         return out
 
+    # -- compact observation records (obs_compact.CompactObs) ---------------------------
+    def grid_snapshot(self) -> torch.Tensor:
+        """The envs' grids [N, R, C] int8 as they stand now (heist_export's grid alone): what
+        heist_obs_expand reads channel 0 from, valid for records packed until the next
+        set_layout."""
+        gr = torch.empty((self.n_envs, self.rows, self.cols), dtype=torch.int8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_export(self._h, None, nat.ptr(gr), None, None, None, self._stream()),
+                      "heist_export")
+        return gr
+
+    def pack_obs(self, obs: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """heist_obs_pack: observation rows [..., 3, R, C] float32 of this env (one tick's
+        [N, 3, R, C], or a step_multi launch's [K, N, 3, R, C]) -> records [..., W] int32, W =
+        heist_obs_record_bytes / 4.  out: a contiguous int32 tensor of that shape to write into."""
+        from .obs_compact import record_words
+        tail = (3, self.rows, self.cols)
+        if (tuple(obs.shape[-3:]) != tail or obs.dtype != torch.float32 or obs.device != self.device
+                or not obs.is_contiguous()):
+            raise ValueError("pack_obs: obs must be a contiguous float32 [..., %d, %d, %d] tensor on %s"
+                             % (tail + (self.device,)))
+        shape = tuple(obs.shape[:-3]) + (record_words(self.rows, self.cols),)
+        if out is None:
+            out = torch.empty(shape, dtype=torch.int32, device=self.device)
+        elif (tuple(out.shape) != shape or out.dtype != torch.int32 or out.device != self.device
+              or not out.is_contiguous()):
+            raise ValueError("pack_obs: out must be a contiguous int32 %s tensor on %s" % (shape, self.device))
+        n = obs.numel() // (3 * self.rows * self.cols)
+        vr, vc = self.config.vault_pos
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_obs_pack(nat.ptr(obs), n, self.rows, self.cols, vr, vc, nat.ptr(out),
+                                               self._stream()), "heist_obs_pack")
+        return out
+
     def count_samples(self, counter: Optional[torch.Tensor]) -> None:
         """Instrumentation (no reference counterpart): later step/reset calls add the number of
         ray samples env e evaluates to ``counter[e]`` (int64 [n_envs] on this device, zeroed by
