@@ -245,7 +245,9 @@ int heist_fast_dir(const double* angle_deg, int64_t n, float* cos_out, float* si
  *   cam_params [3] or [n][3] float32 = fov, speed, heading (cam_stride 0 or 3);
  *   budget [n] int32.  Outputs are the heist_set_layout input arrays with capacities
  *   max_walls / max_cams / max_guards / max_path (max_path >= 8); lists longer than a
- *   capacity are truncated, so size capacities from the budget (budget, /3, /5). */
+ *   capacity are truncated, so size capacities from the budget (budget, /3, /5).  Only the
+ *   first n_walls / n_cams / n_guards entries of an env are written; with allow_cams or
+ *   allow_guards 0 that list's count is 0 (its assets still cost their budget in the scan). */
 int heist_architect_decode(const int64_t* asset_map, int n, int rows, int cols, const float* cam_params,
                            int cam_stride, const int32_t* budget, int allow_cams, int allow_guards, int max_walls,
                            int max_cams, int max_guards, int max_path, int32_t* wall_rc, int32_t* n_walls,

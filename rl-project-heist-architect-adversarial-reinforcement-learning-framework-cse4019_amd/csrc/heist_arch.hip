@@ -38,14 +38,14 @@ __global__ __launch_bounds__(64) void arch_decode_kernel(
         ++nw;
         remaining -= 1;
       } else if (t == 2 && remaining >= 3) {  // camera, vision_range 6
-        if (nc < max_cams) {
+        if (allow_cams && nc < max_cams) {  // a filtered list stays empty: nothing is written past its count
           double* o = cam_out + ((size_t)e * max_cams + nc) * 6;
           o[0] = r; o[1] = c; o[2] = fov; o[3] = heading; o[4] = speed; o[5] = 6.0;
         }
         ++nc;
         remaining -= 3;
       } else if (t == 3 && remaining >= 5) {  // guard: 8-point rectangle patrol (networks.py:324-335)
-        if (ng < max_guards) {
+        if (allow_guards && ng < max_guards) {
           int32_t* pth = guard_paths + ((size_t)e * max_guards + ng) * max_path * 2;
           const int offs[8][2] = {{0, 0}, {0, 1}, {0, 2}, {1, 2}, {2, 2}, {2, 1}, {2, 0}, {1, 0}};
           for (int k = 0; k < 8 && k < max_path; ++k) {

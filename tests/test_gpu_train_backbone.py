@@ -18,25 +18,32 @@ from heist_amd.networks import SolverNetwork
 pytestmark = pytest.mark.gpu
 
 
-def _twins(R, dev, sd=None, seed=0, mfma=True):
+def _rc(grid):
+    """(rows, cols) of a grid given as one side (square) or as a pair."""
+    return (grid, grid) if isinstance(grid, int) else tuple(grid)
+
+
+def _twins(grid, dev, sd=None, seed=0, mfma=True):
+    R, C = _rc(grid)
     torch.manual_seed(seed)
-    a = SolverNetwork(R, R).to(dev).to(memory_format=torch.channels_last)
+    a = SolverNetwork(R, C).to(dev).to(memory_format=torch.channels_last)
     a.mfma_train = mfma
     if sd is not None:
         a.load_state_dict(sd)
-    b = SolverNetwork(R, R).to(dev).to(memory_format=torch.channels_last)
+    b = SolverNetwork(R, C).to(dev).to(memory_format=torch.channels_last)
     b.load_state_dict(a.state_dict())
     b.fused_tail = False
     return a, b
 
 
-def _states(n, R, dev, seed):
+def _states(n, grid, dev, seed):
     """observation-like planes: tile / 5, 0/1 visibility, position channel (environment.py:305-374)"""
+    R, C = _rc(grid)
     g = torch.Generator().manual_seed(seed)
-    x = torch.zeros(n, 3, R, R)
-    x[:, 0] = torch.randint(0, 6, (n, R, R), generator=g).float() / 5
-    x[:, 1] = (torch.rand(n, R, R, generator=g) < 0.3).float()
-    x[:, 2] = -0.3 * torch.rand(n, R, R, generator=g)
+    x = torch.zeros(n, 3, R, C)
+    x[:, 0] = torch.randint(0, 6, (n, R, C), generator=g).float() / 5
+    x[:, 1] = (torch.rand(n, R, C, generator=g) < 0.3).float()
+    x[:, 2] = -0.3 * torch.rand(n, R, C, generator=g)
     return x.to(dev).contiguous(memory_format=torch.channels_last)
 
 
@@ -47,18 +54,23 @@ def _close(got, want, tol, what):
     return err / scale
 
 
-@pytest.mark.parametrize("R", [20, 10, 32])
+@pytest.mark.parametrize("R", [20, 10, 32, pytest.param((13, 17), id="13x17"), pytest.param((16, 18), id="16x18")])
 def test_fused_tail_forward_backward_matches_torch(gpu_device, R):
     """The MIOpen + fused-tail path (_BackboneF32; the MFMA path off): features() and every
-    backbone gradient of sum(features * V) (V fixed random) on 384 states vs plain torch,
-    relative to each tensor's max within 1e-5 (forward) and 1e-4 (gradients).  R = 10 has
-    overlapping pool windows (10 % 4 != 0).  Both sides run MIOpen's convolutions, so their
-    ReLU masks agree."""
-    n = 384
-    a, b = _twins(R, gpu_device, seed=R, mfma=False)
+    backbone gradient of sum(features * V) (V fixed random) on 384 states (64 on the two
+    rectangular grids) vs plain torch, relative to each tensor's max within 1e-5 (forward) and
+    1e-4 (gradients).  R = 10 has overlapping pool windows (10 % 4 != 0); 13 x 17 overlaps on
+    both sides and 16 x 18 on one (rows a multiple of 4, columns not): the only place the tail
+    meets MIOpen's real strides on a non-square grid.  Both sides run MIOpen's convolutions, so
+    their ReLU masks agree."""
+    square = isinstance(R, int)
+    n = 384 if square else 64
+    seed = R if square else 100 * R[0] + R[1]
+    a, b = _twins(R, gpu_device, seed=seed, mfma=False)
     x2 = _states(2, R, gpu_device, 0)
+    assert tuple(x2.shape[2:]) == _rc(R)
     assert a._fused_tail_ok(x2) and not b._fused_tail_ok(x2) and not a._train_conv_ok(x2)
-    x = _states(n, R, gpu_device, seed=R + 1)
+    x = _states(n, R, gpu_device, seed=seed + 1)
     V = torch.randn(n, 256, device=gpu_device, generator=torch.Generator(device=gpu_device).manual_seed(3))
     fa, fb = a.features(x), b.features(x)
     _close(fa, fb, 1e-5, "features")
@@ -68,7 +80,7 @@ def test_fused_tail_forward_backward_matches_torch(gpu_device, R):
     for (n, p), q in zip(a.named_parameters(), b.parameters()):
         if n.startswith(("conv", "fc_spatial")):
             worst = max(worst, _close(p.grad, q.grad, 1e-4, n))
-    print("R=%d worst relative gradient difference %.3g" % (R, worst))
+    print("grid %s worst relative gradient difference %.3g" % (R, worst))
 
 
 def _mfma_forward(net, x):
