@@ -114,6 +114,52 @@ int heist_step_multi(heist_t h, int K, const int64_t* actions, float* obs_out, f
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,
                  double* guard_heading, heist_stream_t stream);
 
+/* Env state blobs, no reference counterpart as an entry point: a restatement of everything
+ * HeistEnvironment.reset / step read and write (environment.py:183-299: solver_pos, tick, done,
+ * solver_detected, vault_reached, _prev_dist, _initial_dist, every camera's heading, every guard's
+ * current_idx and heading) together with the layout they run on (environment.py:102-152: grid,
+ * cameras, guards and their patrol paths, the budget spent), so that a saved env can be put back,
+ * moved to another handle or process, or forked.
+ * After heist_state_load every later heist_step, heist_step_multi, heist_reset, heist_export,
+ * heist_obs_pack of its rows and heist_set_layout on a loaded env gives, bit for bit, what the
+ * saved env would have given from the moment of heist_state_save -- on the same handle after its
+ * layouts changed, on another handle, in another process -- provided the handle was created with
+ * the same heist_create arguments (n_envs apart) and the same guard-cone setting.  Knobs that do
+ * not change results may differ (HEIST_STEP_WAVES, HEIST_LEAN, HEIST_LEAN_WAVES, HEIST_STEP_LEAN,
+ * the ray mode).  Sample counters and stamps are instrumentation, not state: not saved.
+ * One blob is heist_state_bytes(h) bytes, a multiple of 16 and a function of rows, cols, max_cams,
+ * max_guards, max_path, the guard-cone setting and the format version (944 B at 20 x 20 with
+ * max_cams 5, max_guards 3, max_path 8; 1,696 B at 32 x 32 with the same; -1 on a bad handle):
+ *   64 B   header: 16 little-endian uint32 = magic 0x54534548, format version 1, rows, cols,
+ *          max_cams, max_guards, max_path, guard_cones, max_steps, start r, c, vault r, c, 0, 0, 0
+ *   48 B   the 12 int32 scalars of heist_export
+ *   32 B x max_cams    fov, heading, speed (float64), row, col, range, rays (int16)
+ *   32 B x max_guards  fov, heading (float64), patrol index, step, length, range, rays (int16),
+ *                      position, patrol start (uint16 r | c << 8), two cone-cache slots (uint8)
+ *   2 B x max_guards x max_path patrol points (r | c << 8), padded to 16 B
+ *   rows x cols B      grid (int8 tiles), padded to 16 B
+ *   the bit-packed raycast stop map of the grid with its 6-cell border, padded to 16 B
+ * The guard cone cache (8 KB per guard) is not in the blob: a load rebuilds it with the kernel
+ * heist_set_layout uses, recomputes the dispatch order and marks the K-tick fan table stale, as
+ * heist_set_layout does.
+ * heist_state_save: blobs [m][bytes] (16-byte aligned), blob i = env env_ids[i] (int32, device;
+ *   NULL: envs 0..m-1).  Reads the env only.  An env id outside [0, n_envs) gives a blob of zeros,
+ *   which no load accepts.
+ * heist_state_load: env env_ids[i] (NULL: i) <- blob blob_index[i] (int32, device; NULL: i) of
+ *   blobs [n_blobs][bytes]; a fork is blob_index naming one blob many times.  status_out [m] uint8
+ *   (may be NULL): 1 loaded, 0 rejected with the env left untouched -- an env id outside
+ *   [0, n_envs), an env named by more than one item (all of them are rejected), a blob index
+ *   outside [0, n_blobs), a header that differs from the handle's in any word, or records that do
+ *   not fit the handle's capacities.  blobs must stay unchanged until the call's work on `stream`
+ *   is done.  Two loads on one handle must not run concurrently on different streams (they share
+ *   the handle's scratch).
+ * HEIST_EINVAL: m < 0, n_blobs < 0, blobs NULL with m > 0, blobs not 16-byte aligned, a save of
+ * m > n_envs without env_ids.  m == 0 is a no-op. */
+int64_t heist_state_bytes(heist_t h);
+int heist_state_save(heist_t h, const int32_t* env_ids, int m, void* blobs, heist_stream_t stream);
+int heist_state_load(heist_t h, const int32_t* env_ids, int m, const void* blobs, int n_blobs,
+                     const int32_t* blob_index, uint8_t* status_out, heist_stream_t stream);
+
 /* Compact observation records, no reference counterpart as an entry point: a lossless restatement
  * of get_state_tensor's output (environment.py:305-374) for callers that keep many observations
  * (the trainer's rollout buffer).  Channel 0 is grid / 5 and constant while a layout stands, channel

@@ -88,6 +88,13 @@ hipError_t launch_rollout_tally(const uint8_t* valid, int32_t* attempts, int A, 
                                 int det, hipStream_t st);
 hipError_t launch_lstm_cell(const float* gx, const float* gh, const float* c, float* h1, float* c1, int H, int n,
                             hipStream_t st);
+int64_t state_blob_bytes(const EnvParams& p);
+hipError_t launch_state_save(const EnvParams& p, const int32_t* env_ids, int m, void* blobs, hipStream_t st);
+hipError_t launch_state_load(const EnvParams& p, const int32_t* env_ids, int m, const void* blobs, int n_blobs,
+                             const int32_t* blob_index, uint8_t* status_out, uint8_t* loaded, int32_t* src,
+                             hipStream_t st);
+hipError_t launch_state_guards(const EnvParams& p, const void* blobs, const uint8_t* loaded, const int32_t* src,
+                               hipStream_t st);
 int obs_record_words(int R, int C);
 hipError_t launch_obs_pack(const float* obs, int64_t n, int R, int C, int vr, int vc, uint32_t* rec, hipStream_t st);
 hipError_t launch_obs_expand(const uint32_t* rec, int64_t n_rec, const int32_t* rec_env, const int64_t* index, int64_t m,
@@ -104,8 +111,10 @@ using heist::EnvParams;
 struct heist_env {
   int device;
   EnvParams p;
-  void* allocs[12];
+  void* allocs[13];
   int n_allocs;
+  int32_t* state_src;      // heist_state_load scratch [n_envs]: the blob each loaded env takes its guards from
+  uint8_t* state_loaded;   // and [n_envs]: 1 for the envs the launch loaded (guard_cone_kernel's mask)
   int fan_pos;             // next entry of the shared fan table (FanTick) for a K-tick launch; -1: refill first
   hipStream_t fan_stream;  // stream of the K-tick launch that last used the table (a refill on another stream
                            // could overwrite entries a launch still in flight on this one reads)
@@ -293,6 +302,7 @@ int heist_create(int R, int C, int max_steps, int sr, int sc, int vr, int vc, co
       // guard cone cache: 64 B per (guard, patrol index, heading slot)
       sizeof(uint16_t) * heist::kConeEntry * n * (max_guards > 0 ? max_guards : 1) * heist::kConePath * heist::kConeSlots,
       sizeof(heist::FanTick) * heist::kFanTicks,
+      (sizeof(int32_t) + 1) * n,  // heist_state_load scratch: src [n] int32, loaded [n] uint8
   };
   static_assert(sizeof(sizes) / sizeof(sizes[0]) <= sizeof(((heist_env*)nullptr)->allocs) / sizeof(void*),
                 "heist_env::allocs too small");
@@ -321,6 +331,8 @@ int heist_create(int R, int C, int max_steps, int sr, int sc, int vr, int vc, co
   p.stop_bytes = heist::stop_map_bytes(R, C);
   p.cones = (uint16_t*)h->allocs[10];
   p.fan = (heist::FanTick*)h->allocs[11];
+  h->state_src = (int32_t*)h->allocs[12];
+  h->state_loaded = (uint8_t*)(h->state_src + n);
   h->fan_pos = -1;
   h->fan_stream = nullptr;
   h->fan_used = false;
@@ -473,6 +485,45 @@ int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading,
   if (int rc = check_handle(h)) return rc;
   return check_hip(heist::launch_export(h->p, scalars, grid, cam_heading, guard_idx, guard_heading, (hipStream_t)stream),
                    "heist_export");
+}
+
+int64_t heist_state_bytes(heist_t h) {
+  if (check_handle(h)) return -1;
+  return heist::state_blob_bytes(h->p);
+}
+
+int heist_state_save(heist_t h, const int32_t* env_ids, int m, void* blobs, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(m >= 0, "heist_state_save: m < 0");
+  if (m == 0) return 0;
+  HEIST_REQUIRE(blobs != nullptr, "heist_state_save: blobs is null");
+  HEIST_REQUIRE(((uintptr_t)blobs & 15) == 0, "heist_state_save: blobs must be 16-byte aligned");
+  HEIST_REQUIRE(env_ids != nullptr || m <= h->p.n_envs, "heist_state_save: m > n_envs without env_ids");
+  return check_hip(heist::launch_state_save(h->p, env_ids, m, blobs, (hipStream_t)stream), "heist_state_save");
+}
+
+int heist_state_load(heist_t h, const int32_t* env_ids, int m, const void* blobs, int n_blobs,
+                     const int32_t* blob_index, uint8_t* status_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(m >= 0 && n_blobs >= 0, "heist_state_load: m < 0 or n_blobs < 0");
+  if (m == 0) return 0;
+  HEIST_REQUIRE(blobs != nullptr, "heist_state_load: blobs is null");
+  HEIST_REQUIRE(((uintptr_t)blobs & 15) == 0, "heist_state_load: blobs must be 16-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  h->fan_pos = -1;  // other cameras: the shared fan table is refilled by the next K-tick launch
+  if (int rc = check_hip(hipMemsetAsync(h->state_loaded, 0, (size_t)h->p.n_envs, st), "heist_state_load: scratch"))
+    return rc;
+  if (int rc = check_hip(heist::launch_state_load(h->p, env_ids, m, blobs, n_blobs, blob_index, status_out,
+                                                   h->state_loaded, h->state_src, st),
+                          "heist_state_load"))
+    return rc;
+  // the cone cache of the loaded envs, by the kernel heist_set_layout uses, then the guards' saved pose
+  if (int rc = check_hip(heist::launch_guard_cones(h->p, h->state_loaded, st), "heist_state_load: guard cones"))
+    return rc;
+  if (int rc = check_hip(heist::launch_state_guards(h->p, blobs, h->state_loaded, h->state_src, st),
+                          "heist_state_load: guards"))
+    return rc;
+  return check_hip(heist::launch_order(h->p, st), "heist_state_load: order");
 }
 
 int heist_count_samples(heist_t h, uint64_t* counter) {

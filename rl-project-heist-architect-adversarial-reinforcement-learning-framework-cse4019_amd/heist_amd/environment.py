@@ -169,6 +169,42 @@ class HeistEnvironment:
             self.detection_events.append({"tick": tick_before, "position": self.solver_pos})
         return self._get_observation(), reward, self.done, info
 
+    # -- saved states -----------------------------------------------------------------
+    def get_state(self):
+        """The env as it stands, as an EnvState of one blob (heist_state_save).  Its extra holds
+        what the device does not keep: the observation of the current tick and the host mirror of
+        the layout (the reference's Wall / Camera / Guard lists and the budget)."""
+        import copy
+        st = self._vec.save_state()
+        st.extra = {"obs": self._vec.obs[0].clone(), "walls": copy.deepcopy(self.walls),
+                    "cameras": copy.deepcopy(self.cameras), "guards": copy.deepcopy(self.guards),
+                    "budget_total": self.budget.total_budget, "detection_events": copy.deepcopy(self.detection_events)}
+        return st
+
+    def set_state(self, state) -> None:
+        """Put a get_state() result back (heist_state_load); the host mirrors follow the device:
+        the grid, solver_pos, tick, done and the flags, camera and guard poses, the observation;
+        solver_path restarts at the current cell."""
+        import copy
+        if len(state) != 1:
+            raise ValueError("set_state: expected one saved env, got %d" % len(state))
+        ok = self._vec.load_state(state)
+        if not bool(ok[0].item()):
+            raise RuntimeError("set_state: the device rejected the saved state")
+        ex = state.extra
+        if "walls" in ex:
+            self.walls, self.cameras, self.guards = (copy.deepcopy(ex[k]) for k in ("walls", "cameras", "guards"))
+            self.budget = BudgetManager(total_budget=ex["budget_total"])
+        if "obs" in ex:
+            self._vec.obs[0].copy_(ex["obs"].to(self._vec.device))
+        st = self._vec.export(grid=True)
+        self.grid = st["grid"][0].cpu().numpy().astype(np.int32)
+        self.budget.spent = int(st["spent"][0].item())
+        self.visibility_map.reset()
+        self._pull()
+        self.solver_path = [self.solver_pos]
+        self.detection_events = copy.deepcopy(ex.get("detection_events", []))
+
     # -- observations ---------------------------------------------------------------
     def _get_observation(self) -> Dict[str, np.ndarray]:  # environment.py:305-345
         cfg = self.config

@@ -45,6 +45,7 @@ import torch
 from . import dist_utils
 from .agents.architect import ArchitectAgent
 from .agents.solver import Rollout, SolverAgent
+from .env_state import EnvState, env_checkpoint_path
 from .environment import EnvironmentConfig, HeistEnvironment, accept_layout
 from .obs_compact import CompactObs, record_words
 from .rewards import RewardCalculator
@@ -157,7 +158,7 @@ class AdversarialTrainer:  # training.py:115-790
                  rollout_len: Optional[int] = None, minibatch: int = 4096, device=None, max_budget: Optional[int] = None,
                  seed: Optional[int] = None, update_precision: str = "fp32", rollout_precision: str = "fp32",
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
-                 solver_cadence: str = "rollout", obs_storage: str = "full"):
+                 solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -190,6 +191,12 @@ class AdversarialTrainer:  # training.py:115-790
         if obs_storage not in ("full", "compact"):
             raise ValueError("obs_storage must be 'full' or 'compact'")
         self.obs_storage = obs_storage
+        # True: a checkpoint also holds the batch -- every env's state (HeistEnv.save_state), the
+        # per-env bookkeeping, the LSTM state and the current observation -- in env_ep{N}.pt (one
+        # shard per rank, env_ep{N}_rank{r}.pt, in a multi-rank run), and a resume that finds the
+        # file continues the layouts where they stood instead of drawing new ones
+        self.checkpoint_env = bool(checkpoint_env)
+        self._env_restored = False
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -680,10 +687,14 @@ class AdversarialTrainer:  # training.py:115-790
         self.global_episode = start_episode
         if start_episode == 0:
             self._run_warmup(warmup_rollouts)
-        self._init_batch_state()
+        restored = self._env_restored and start_episode != 0  # the checkpoint's batch stands: no new layouts
+        self._env_restored = False
+        if not restored:
+            self._init_batch_state()
         self._callback = callback
         try:
-            self._assign_layouts(np.arange(self.n_envs))
+            if not restored:
+                self._assign_layouts(np.arange(self.n_envs))
             t0 = time.time()
             next_ckpt = start_episode + 50
             while self.global_episode < start_episode + self.total_episodes:  # a global count: same on every rank
@@ -784,6 +795,18 @@ class AdversarialTrainer:  # training.py:115-790
             out.append(([], [], []) if lay is None else _lb_rows(lay[0], [lay[1]]).to_lists()[0])
         return out
 
+    def _all_layout_lists(self) -> List:
+        """layout_lists of every env, with one device read per LayoutBatch the envs point into."""
+        out = [([], [], [])] * self.n_envs
+        groups = {}
+        for e, lay in enumerate(self.b_layout):
+            if lay is not None:
+                groups.setdefault(id(lay[0]), (lay[0], []))[1].append((e, lay[1]))
+        for lb, items in groups.values():
+            for (e, _), lists in zip(items, _lb_rows(lb, [r for _, r in items]).to_lists()):
+                out[e] = lists
+        return out
+
     def simulate_episode(self, budget: int = 15, solver_attempts: int = 1) -> Dict:  # training.py:713-790
         if self._single_env is None:
             self._single_env = HeistEnvironment(self.config, device=self.device)
@@ -852,6 +875,60 @@ class AdversarialTrainer:  # training.py:115-790
                 with open(lp) as f:
                     self.game_log = [GameLogEntry(**e) for e in json.load(f)]
         self.global_episode = episode
+        self._env_restored = self.checkpoint_env and self._load_env_checkpoint(episode)
+        return True
+
+    # the per-env bookkeeping tensors an env checkpoint holds beside the env states
+    _ENV_CKPT_TENSORS = ("b_valid", "b_attempts", "b_scored", "b_solve", "b_detect", "b_timeout", "b_steps", "b_reward",
+                         "b_logp", "b_value", "h", "c")
+
+    def _env_checkpoint_path(self, episode: int) -> str:
+        return env_checkpoint_path(self.save_dir, episode, dist_utils.rank(), dist_utils.world_size())
+
+    def _save_env_checkpoint(self, episode: int) -> str:
+        """This rank's batch as it stands (checkpoint_env): env states, bookkeeping, LSTM state,
+        the current observation, the episode counter and the Solver's sampling counters."""
+        sd = {"format": "heist_env_checkpoint", "n_envs": self.n_envs, "episode": int(episode),
+              "env_state": self.env.save_state().cpu().state_dict(),
+              "obs": self.env.obs.cpu(), "global_episode": int(self.global_episode),
+              "b_episode": self.b_episode.copy(), "b_meta": list(self.b_meta),
+              "layouts": self._all_layout_lists(), "layout_set": [x is not None for x in self.b_layout],
+              "act_counter": getattr(self.solver, "_act_counter", None),
+              "act_seed": getattr(self.solver, "_act_seed", None)}
+        for k in self._ENV_CKPT_TENSORS:
+            sd[k] = getattr(self, k).cpu()
+        path = self._env_checkpoint_path(episode)
+        torch.save(sd, path)
+        return path
+
+    def _load_env_checkpoint(self, episode: int) -> bool:
+        """Restore _save_env_checkpoint's file of this rank if it exists (else False: the batch
+        is left as it is and the run draws new layouts, as without the option)."""
+        path = self._env_checkpoint_path(episode)
+        if not os.path.exists(path):
+            return False
+        sd = torch.load(path, map_location="cpu", weights_only=False)
+        if sd.get("format") != "heist_env_checkpoint" or int(sd["n_envs"]) != self.n_envs:
+            raise ValueError("%s: not an env checkpoint of %d envs" % (path, self.n_envs))
+        status = self.env.load_state(EnvState.from_state_dict(sd["env_state"]))
+        if not bool(status.all()):
+            raise RuntimeError("%s: the device rejected %d saved envs" % (path, int((~status).sum())))
+        self.env.obs.copy_(sd["obs"])
+        for k in self._ENV_CKPT_TENSORS:
+            setattr(self, k, sd[k].to(self.device).contiguous())
+        self.b_episode = np.asarray(sd["b_episode"], np.int64).copy()
+        self.b_meta = list(sd["b_meta"])
+        # the host copy of the layouts (frames, layout_lists): one LayoutBatch rebuilt from the saved lists
+        from .vec_env import LayoutBatch
+        env = self.env
+        budgets = [m[1] if m else self.config.architect_budget for m in self.b_meta]
+        lb = LayoutBatch.from_lists(sd["layouts"], budgets, env.max_cams, env.max_guards, env.max_path, self.device,
+                                    env.rows, env.cols)
+        self.b_layout = [(lb, e) if on else None for e, on in enumerate(sd["layout_set"])]
+        self.global_episode = int(sd["global_episode"])
+        for name, key in (("_act_counter", "act_counter"), ("_act_seed", "act_seed")):
+            if sd.get(key) is not None and hasattr(self.solver, name):
+                setattr(self.solver, name, sd[key])
         return True
 
     def resume_from_checkpoint(self) -> int:
@@ -891,6 +968,8 @@ class AdversarialTrainer:  # training.py:115-790
         if dist_utils.rank() == 0:
             self.architect.save(os.path.join(self.save_dir, "architect_ep%d.pt" % episode))
             self.solver.save(os.path.join(self.save_dir, "solver_ep%d.pt" % episode))
+        if self.checkpoint_env:
+            self._save_env_checkpoint(episode)
         self._save_metrics()
         self._save_game_log()
 

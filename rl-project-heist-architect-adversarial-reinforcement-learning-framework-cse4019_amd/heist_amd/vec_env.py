@@ -314,6 +314,63 @@ class HeistEnv:
             out["grid"] = gr
         return out
 
+    # -- saved states (env_state.EnvState) ------------------------------------------------
+    def state_config(self) -> dict:
+        """What a saved state depends on: the heist_create arguments (n_envs apart), the
+        guard-cone setting, the blob format version and size."""
+        from .env_state import FORMAT_VERSION
+        cfg = self.config
+        b = int(nat.lib().heist_state_bytes(self._h))
+        nat.check(0 if b > 0 else b, "heist_state_bytes")
+        return {"rows": self.rows, "cols": self.cols, "max_cams": self.max_cams, "max_guards": self.max_guards,
+                "max_path": self.max_path, "guard_cones": self.kernel_config()["guard_cones"],
+                "max_steps": cfg.max_steps, "start_r": cfg.start_pos[0], "start_c": cfg.start_pos[1],
+                "vault_r": cfg.vault_pos[0], "vault_c": cfg.vault_pos[1], "version": FORMAT_VERSION, "bytes": b}
+
+    def _ids(self, ids, what):
+        if ids is None:
+            return None
+        t = torch.as_tensor(ids).reshape(-1).to(device=self.device, dtype=torch.int32).contiguous()
+        if t.numel() == 0:
+            raise ValueError("%s: empty index list" % what)
+        return t
+
+    def save_state(self, env_ids=None):
+        """heist_state_save: the envs env_ids (None: all, in order) as an EnvState on this device.
+        Reads the envs only.  The observation (env.obs) is an output, not state: keep it yourself
+        if the next action is chosen from it."""
+        from .env_state import EnvState
+        cfg = self.state_config()
+        ids = self._ids(env_ids, "save_state")
+        m = self.n_envs if ids is None else int(ids.numel())
+        blobs = torch.empty((m, cfg["bytes"]), dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_state_save(self._h, nat.ptr(ids), m, nat.ptr(blobs), self._stream()),
+                      "heist_state_save")
+        return EnvState(blobs, cfg)
+
+    def load_state(self, state, env_ids=None, index=None) -> torch.Tensor:
+        """heist_state_load: env env_ids[i] (None: i) <- blob index[i] (None: i) of state; a fork
+        is index naming one blob many times.  Returns status [m] bool on this device: False where
+        the device rejected the item (env id out of range or named twice, blob index out of
+        range, a blob whose header or records do not fit) and left the env untouched.  Raises
+        HeistError, before any launch, when state was saved under another configuration."""
+        state.check(self.state_config())
+        ids, idx = self._ids(env_ids, "load_state"), self._ids(index, "load_state")
+        if ids is not None and idx is not None and ids.numel() != idx.numel():
+            raise ValueError("load_state: %d env ids for %d blob indices" % (ids.numel(), idx.numel()))
+        m = int(ids.numel()) if ids is not None else (int(idx.numel()) if idx is not None else len(state))
+        blobs = state.blobs
+        if blobs.device != self.device:
+            blobs = blobs.to(self.device)
+        if blobs.data_ptr() % 16:
+            blobs = blobs.clone()
+        status = torch.zeros(m, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_state_load(self._h, nat.ptr(ids), m, nat.ptr(blobs), len(state), nat.ptr(idx),
+                                                 nat.ptr(status), self._stream()), "heist_state_load")
+        return status.view(torch.bool)
+
     # -- compact observation records (obs_compact.CompactObs) ---------------------------
     def grid_snapshot(self) -> torch.Tensor:
         """The envs' grids [N, R, C] int8 as they stand now (heist_export's grid alone): what
