@@ -428,7 +428,18 @@ int heist_solver_features(const float* obs, int n, int rows, int cols, const voi
  * heist_solver_head: feat [n][1024] (heist_solver_features), h_in / c_in [n][128] or NULL
  * (zero state); seed / counter select the sample (counter-based hash, one uniform per env);
  * outputs logits [n][A] (may be NULL), value [n], action [n] int64, logp [n],
- * h_out / c_out [n][128] (must not alias h_in / c_in). */
+ * h_out / c_out [n][128] (must not alias h_in / c_in).  h_in and c_in are independently
+ * optional; rows past n - 1 of no output are written; n == 0 is a no-op.
+ * The draw is part of the contract (saved runs replay it): for env e of the batch,
+ *   z = mix64(seed ^ counter * 0xD1B54A32D192ED03 ^ e * 0x9E3779B97F4A7C15)   (mod 2^64),
+ *   mix64(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB;
+ *             z ^= z >> 31                                     (the splitmix64 finaliser),
+ *   u = (z >> 40) * 2^-24                                      (the top 24 bits, 0 <= u < 1),
+ * with p = softmax(logits) in fp32 and S = p_0 + ... + p_{A-1},
+ *   action = the first a with u * S < p_0 + ... + p_a, else A - 1
+ * (strict: a draw on a boundary takes the action above it, and an action of probability 0
+ * is never taken), and logp = log(clamp(p_action / S, eps, 1 - eps)) with eps = 2^-23
+ * (fp32 epsilon), which is torch's Categorical(probs=p).log_prob(action). */
 /* Instrumentation, no reference counterpart: with buf a device array of
  * n_workgroups * 4 * 10 uint64, later heist_solver_features launches record s_memtime at
  * 10 phase points of each wave for its workgroup's second env (tools/probe_policy.py);

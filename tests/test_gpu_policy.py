@@ -13,34 +13,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from heist_amd import EnvironmentConfig, HeistEnv
 from heist_amd.agents import SolverAgent
-from heist_amd.layouts import synthetic_layouts
 from heist_amd.networks import SolverNetwork
+from policy_ref import (TOL_EMU_MAX, TOL_EMU_MEAN, TOL_F32_MAX, _big_heads, _rel, emulate_backbone, emulate_head,
+                        env_obs)
 
 pytestmark = pytest.mark.gpu
-
-# bf16 has an 8-bit significand: one rounding is <= 2^-9 relative.  Against the emulation
-# only accumulation order differs, which can flip a bf16 rounding of an activation
-# (one ulp, 2^-8) on rare elements; pooling averages those.
-TOL_EMU_MAX = 4e-3    # max |kernel - emulation| / max |emulation|
-TOL_EMU_MEAN = 2e-4   # mean |kernel - emulation| / max |emulation|
-TOL_F32_MAX = 3e-2    # max |kernel - fp32 torch| / max |fp32 torch|
-
-
-def _bf(x):
-    return x.to(torch.bfloat16).to(x.dtype)
-
-
-def emulate_backbone(net, obs):
-    """float64 CPU restatement of the kernel's arithmetic (rounding points as the kernel)."""
-    x = _bf(obs.detach().double().cpu())
-    convs = (net.conv1, net.conv2, net.conv3)
-    for conv in convs:
-        w = _bf(conv.weight.detach().double().cpu())
-        b = conv.bias.detach().float().double().cpu()
-        x = _bf(F.relu(F.conv2d(x, w, b, padding=1)))
-    return F.adaptive_avg_pool2d(x, (4, 4)).reshape(x.shape[0], -1)
 
 
 def torch_backbone(net, obs):
@@ -49,24 +27,6 @@ def torch_backbone(net, obs):
         x = F.relu(net.conv2(x))
         x = F.relu(net.conv3(x))
         return net.pool(x).reshape(obs.shape[0], -1)
-
-
-def env_obs(n, R, device, seed=0, steps=5):
-    cfg = EnvironmentConfig(grid_rows=R, grid_cols=R)
-    env = HeistEnv(n, cfg, device=device)
-    env.set_layouts(synthetic_layouts(n, R, R, 15 if R >= 20 else 5, seed=seed))
-    env.reset()
-    g = torch.Generator(device=device)
-    g.manual_seed(seed)
-    for _ in range(steps):
-        env.step(torch.randint(0, 5, (n,), device=device, generator=g))
-    return env.obs.clone()
-
-
-def _rel(a, b):
-    d = (a.double().cpu() - b.double().cpu()).abs()
-    m = b.double().abs().max().item()
-    return d.max().item() / m, d.mean().item() / m
 
 
 @pytest.mark.parametrize("R,n", [(20, 64), (20, 1), (20, 300), (10, 77), (32, 64), (32, 1), (32, 300)])
@@ -192,33 +152,6 @@ def test_unsupported_grid_rejected(gpu_device):
 # ---------------------------------------------------------------------------------
 # fused head: fc_spatial + LSTM cell + heads + Categorical sample (heist_solver_head)
 # ---------------------------------------------------------------------------------
-
-def _big_heads(net):
-    """Head weights with gain 1 (the reference's 0.01-gain init makes logits ~0)."""
-    for m in (net.fc_spatial, net.policy_head[0], net.policy_head[2], net.value_head[0], net.value_head[2]):
-        torch.nn.init.orthogonal_(m.weight, gain=1.0)
-        torch.nn.init.uniform_(m.bias, -0.1, 0.1)
-    return net
-
-
-def emulate_head(net, feat, h, c):
-    """float64 CPU restatement of heist_solver_head's arithmetic (bf16 GEMM operands,
-    fp32 biases with b_ih + b_hh summed in fp32, fp32/fp64 elsewhere)."""
-    W = lambda t: t.detach().double().cpu()  # noqa: E731
-    Bf = lambda t: t.detach().float().double().cpu()  # noqa: E731
-    x = _bf(F.relu(_bf(feat.double().cpu()) @ _bf(W(net.fc_spatial.weight)).T + Bf(net.fc_spatial.bias)))
-    bg = (net.lstm.bias_ih_l0.detach().float() + net.lstm.bias_hh_l0.detach().float()).double().cpu()
-    gates = x @ _bf(W(net.lstm.weight_ih_l0)).T + _bf(h.double().cpu()) @ _bf(W(net.lstm.weight_hh_l0)).T + bg
-    i, f, g, o = gates.chunk(4, 1)
-    c1 = torch.sigmoid(f) * c.double().cpu() + torch.sigmoid(i) * torch.tanh(g)
-    h1 = torch.sigmoid(o) * torch.tanh(c1)
-    hn = _bf(h1)
-    hp = F.relu(hn @ _bf(W(net.policy_head[0].weight)).T + Bf(net.policy_head[0].bias))
-    hv = F.relu(hn @ _bf(W(net.value_head[0].weight)).T + Bf(net.value_head[0].bias))
-    logits = hp @ W(net.policy_head[2].weight).T + Bf(net.policy_head[2].bias)
-    value = (hv @ W(net.value_head[2].weight).T + Bf(net.value_head[2].bias)).reshape(-1)
-    return logits, value, h1, c1
-
 
 @pytest.mark.parametrize("n", [1, 33, 4096])
 def test_head_matches_emulation(gpu_device, n):
