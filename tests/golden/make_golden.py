@@ -31,6 +31,20 @@ Fixture files (all numpy .npz, loaded with allow_pickle=False):
                   and per parameter tensor the gradient left after the update
                   (clipped) and the parameter change, as L2 norms plus 4 fixed
                   random projections (proj_vectors(): data, not weights).
+  solver_update_<case>.npz  (key `update`, or `update:g20,clip20` for some cases)
+                  SolverAgent.update (agents/solver.py:112-217) from the nets.npz
+                  Solver weights on buffers filled by reference episodes on
+                  Architect layouts (select_action / store_transition), cases
+                  g20, g32, g10, clip20, big20 (UPDATE_CASES): the buffers (states
+                  as occupancy codes per layout + visibility bits + position
+                  index, bit-exact), the replayed shuffles, normalised advantages
+                  and returns, the metrics; at the first step, the first short
+                  minibatch and the last step the loss parts, the pre-clip total
+                  norm and gradients (conv tensors in full, the others as L2 norm
+                  + 4 projections); the parameter change likewise; and the
+                  reference's own float32 error against the float64 restatement
+                  tests/solver_update_ref.py per tensor (the tests' noise floor).
+                  One file per case: each stays under 1 MiB.
 """
 import json
 import os
@@ -624,9 +638,218 @@ def make_arch_update():
     np.savez_compressed(os.path.join(OUT, "arch_update.npz"), **arrs)
 
 
+# ---------------------------------------------------------------------------
+# the Solver's whole PPO update
+# ---------------------------------------------------------------------------
+
+# name: (grid, transitions, epochs, batch, architect budget, max_steps, layouts, seed, head scale)
+UPDATE_CASES = {
+    "g20": (20, 129, 3, 64, 15, 14, 4, 410, 1.0),
+    "g32": (32, 86, 3, 64, 27, 14, 3, 411, 1.0),
+    "g10": (10, 70, 3, 64, 5, 9, 3, 412, 1.0),
+    "clip20": (20, 129, 3, 64, 15, 14, 4, 413, 2.8e5),
+    "big20": (20, 4099, 1, 4099, 15, 30, 16, 414, 1.0),
+}
+
+
+def _fill_solver_buffer(ag, R, T, budget, max_steps, n_layouts, seed):
+    """Reference episodes on Architect layouts through select_action / store_transition until
+    the buffer holds T transitions (the last episode is cut there)."""
+    lays = architect_layouts(n_layouts, R, R, budget, seed)
+    torch.manual_seed(seed + 1000)
+    envs = []
+    for lay in lays:
+        env = HeistEnvironment(EnvironmentConfig(grid_rows=R, grid_cols=R, max_steps=max_steps, architect_budget=budget))
+        env.budget.scale_budget(budget)
+        if env.set_layout(*lay):
+            envs.append(env)
+    assert envs, "no valid layout"
+    k = 0
+    while len(ag.rewards) < T:
+        env = envs[k % len(envs)]
+        k += 1
+        env.reset()
+        ag.reset()
+        done, total = False, 0.0
+        while not done and len(ag.rewards) < T:
+            a = ag.select_action(env.get_state_tensor())
+            _, r, done, _ = env.step(a)
+            ag.store_transition(r, done)
+            total += r
+        ag.end_episode(total)
+
+
+def make_solver_update(only=None):
+    """tests/golden/solver_update_<case>.npz: the reference SolverAgent.update() on real buffers."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    import solver_update_ref as sr
+    import heist_architect.agents.solver as solver_mod
+    from types import SimpleNamespace
+
+    for name, (R, T, epochs, batch, budget, max_steps, n_lay, seed, scale) in UPDATE_CASES.items():
+        if only and name not in only:
+            continue
+        torch.manual_seed(seed)
+        ag = SolverAgent(grid_rows=R, grid_cols=R, ppo_epochs=epochs, batch_size=batch)
+        sd = sr.golden_params(scale)
+        ag.network.load_state_dict(sd)
+        _fill_solver_buffer(ag, R, T, budget, max_steps, n_lay, seed)
+        rng = np.random.default_rng(seed)
+        if name == "clip20":  # stale old log-probs on a random third of the rows (as make_ppo)
+            lp = np.array(ag.log_probs, np.float32)
+            lp = (lp + rng.normal(0, 0.3, T) * (rng.random(T) < 1.0 / 3.0)).astype(np.float32)
+            ag.log_probs = [float(v) for v in lp]
+        states = np.array(ag.states, np.float32)
+        actions = np.array(ag.actions, np.int64)
+        logp, values = np.array(ag.log_probs, np.float32), np.array(ag.values, np.float32)
+        rewards, dones = np.array(ag.rewards, np.float32), np.array(ag.dones, bool)
+        assert len(states) == T and dones.sum() >= 3, (len(states), dones.sum())
+        occ, lay, vis, pos = sr.encode_states(states, R, R)
+        assert np.array_equal(sr.decode_states(occ, lay, vis, pos, R, R).view(np.uint32), states.view(np.uint32)), \
+            "state coding does not round-trip"
+        perms = np.stack([rng.permutation(T) for _ in range(epochs)]).astype(np.int32)
+        n_mb = (T + batch - 1) // batch
+        n_steps = epochs * n_mb
+        # recorded steps: the first, the first short (tail) minibatch, the last
+        rec = sorted({0, n_mb - 1, n_steps - 1}) if T % batch and n_mb > 1 else [0]
+
+        # float64 restatement first (its ReLU signs are compared with the reference's as it runs)
+        r64 = sr.run_update(sd, states, actions, logp, values, rewards, dones.astype(np.float32), perms, epochs, batch,
+                            record=rec, keep_signs=True)
+        assert r64["n_steps"] == n_steps
+
+        recorded, flips, state = {}, [], {"step": 0, "perm": 0, "k": 0}
+        real_clip = torch.nn.utils.clip_grad_norm_
+
+        def clip(parameters, max_norm, *a, **kw):
+            parameters = list(parameters)
+            s = state["step"]
+            grads = [p.grad.detach().clone() for p in parameters]
+            total = real_clip(parameters, max_norm, *a, **kw)
+            if s in rec:
+                # the step's loss parts are locals of the reference's update(): this relies on
+                # update() calling clip_grad_norm_ directly and on those three names
+                loc = sys._getframe(1).f_locals
+                recorded[s] = dict(grads=grads, total=float(total),
+                                   parts=np.array([float(loc["policy_loss"]), float(loc["value_loss"]), float(loc["entropy"])]))
+            state["step"] += 1
+            state["k"] = 0
+            return total
+
+        def replay(n):
+            assert n == T
+            state["perm"] += 1
+            return perms[state["perm"] - 1].astype(np.int64)
+
+        def sign_hook(mod, inp, out):
+            if state["k"] == 0:
+                flips.append([0, 0])
+            own = r64["signs"][state["step"]][state["k"]]
+            flips[-1][0] += int(((out.detach() > 0) != own).sum())
+            flips[-1][1] += own.numel()
+            state["k"] += 1
+
+        class _NN:  # the reference module's `nn`, with clip_grad_norm_ wrapped
+            utils = SimpleNamespace(clip_grad_norm_=clip)
+
+            def __getattr__(self, k):
+                return getattr(torch.nn, k)
+
+        hooks = [m.register_forward_hook(sign_hook) for m in (ag.network.conv1, ag.network.conv2, ag.network.conv3)]
+        real_perm, real_nn = np.random.permutation, solver_mod.nn
+        np.random.permutation, solver_mod.nn = replay, _NN()
+        try:
+            metrics = ag.update()
+        finally:
+            np.random.permutation, solver_mod.nn = real_perm, real_nn
+            for hk in hooks:
+                hk.remove()
+        assert state["step"] == n_steps and state["perm"] == epochs and not ag.states
+        after = dict(ag.network.named_parameters())
+        assert list(after) == list(sr.PARAMS)
+
+        adv = ag._compute_gae(torch.tensor(rewards), torch.tensor(values), torch.tensor(dones.astype(np.float32)))
+        ret = (adv + torch.tensor(values)).numpy()
+        adv_n = ((adv - adv.mean()) / (adv.std() + 1e-8)).numpy()
+
+        arrs = dict(cfg=np.array([R, R, T, epochs, batch], np.int64), head_scale=np.float64(scale),
+                    hyper=np.array([sr.HYPER[k] for k in ("lr", "gamma", "lam", "clip", "ecoef", "vcoef", "max_norm")]),
+                    occ=occ, lay=lay, vis=vis, pos=pos, actions=actions.astype(np.int8), logp=logp, values=values,
+                    rewards=rewards, dones=dones, perms=perms, adv=adv_n.astype(np.float32), ret=ret.astype(np.float32),
+                    metrics=np.array([metrics["solver_policy_loss"], metrics["solver_value_loss"],
+                                      metrics["solver_entropy"]], np.float64),
+                    n_steps=np.int64(n_steps), rec_steps=np.array(rec, np.int64),
+                    flips=np.array(flips, np.int64))
+
+        def pack(tensors, key):  # conv tensors in full, every tensor's norm + 4 projections
+            t64 = [t.detach().double().reshape(-1).numpy() for t in tensors]
+            arrs[key + "conv"] = np.concatenate(t64[:sr.N_CONV]).astype(np.float32)
+            arrs[key + "norm"] = np.array([np.linalg.norm(t) for t in t64])
+            arrs[key + "proj"] = np.array([sr.proj_vectors(i, t.size) @ t for i, t in enumerate(t64)])
+
+        # the reference's own fp32 noise against float64: the tests' floors
+        f_max, f_l2, f_tot = [], [], []
+        for s in rec:
+            g32 = recorded[s]["grads"]
+            g64 = [r64["steps"][s]["grads"][k] for k in sr.PARAMS]
+            pack(g32, "s%d_g" % s)
+            arrs["s%d_total" % s] = np.float64(recorded[s]["total"])
+            arrs["s%d_parts" % s] = recorded[s]["parts"]
+            f_max.append([sr.rel_max(a.double().numpy(), b.numpy()) if i != sr.HH else 0.0
+                          for i, (a, b) in enumerate(zip(g32, g64))])
+            f_l2.append([sr.rel_l2(a.double().numpy(), b.numpy()) if i != sr.HH else 0.0
+                         for i, (a, b) in enumerate(zip(g32, g64))])
+            f_tot.append(abs(recorded[s]["total"] - r64["steps"][s]["total_norm"]) / r64["steps"][s]["total_norm"])
+            assert not g32[sr.HH].any() and not g64[sr.HH].any()
+            assert np.abs(recorded[s]["parts"] - r64["steps"][s]["parts"]).max() <= 1e-5, s
+        d32 = [after[k].detach().double() - sd[k].double() for k in sr.PARAMS]
+        d64 = [r64["params"][k] - sd[k].double() for k in sr.PARAMS]
+        pack(d32, "d_")
+        f_d = [sr.rel_l2(a.numpy(), b.numpy()) if i != sr.HH else 0.0 for i, (a, b) in enumerate(zip(d32, d64))]
+        assert not d32[sr.HH].any() and not d64[sr.HH].any()
+        arrs.update(floor_grad_max=np.array(f_max), floor_grad_l2=np.array(f_l2), floor_total=np.array(f_tot),
+                    floor_delta=np.array(f_d), floor_metrics=np.abs(arrs["metrics"] - r64["metrics"]))
+        flip_share = max(f / n for f, n in flips)
+        print("%-6s T=%d steps=%d rec=%s dones=%d layouts=%d | ref fp32 vs float64: grad/max %.2g grad/L2 %.2g "
+              "total %.2g delta/L2 %.2g (scaled heads %.2g) metrics %.2g ReLU sign share %.2g (%d flips) | entropy %.4f total norm %.3g"
+              % (name, T, n_steps, rec, dones.sum(), len(occ), np.max(f_max), np.max(f_l2), np.max(f_tot),
+                 max(v for i, v in enumerate(f_d) if scale == 1.0 or sr.PARAMS[i] not in sr.SCALED),
+                 max(f_d[sr.PARAMS.index(k)] for k in sr.SCALED),
+                 arrs["floor_metrics"].max(), flip_share, sum(f for f, _ in flips), recorded[0]["parts"][2],
+                 recorded[0]["total"]), flush=True)
+        # a head layer scaled to |w| ~ 1e2 .. 3e3 moves by about one float32 spacing of w per Adam
+        # step (lr 3e-4): its change is stored in full and held element by element to half a
+        # spacing per step (round to nearest), not to 1e-4 in relative L2
+        coarse = [sr.PARAMS.index(k) for k in sr.SCALED] if scale != 1.0 else []
+        if coarse:
+            arrs["d_heads"] = np.concatenate([d32[i].reshape(-1).numpy() for i in coarse])
+            for i, (want, allowed) in sr.coarse_delta(arrs, sd, 0.5 * n_steps).items():
+                assert np.array_equal(want, d32[i].reshape(-1).numpy())
+                assert float((np.abs(d64[i].reshape(-1).numpy() - want) / allowed).max()) <= 1.0, (name, sr.PARAMS[i])
+        fine = [v for i, v in enumerate(f_d) if i not in coarse]
+        # a single Adam step is lr * g / (|g| + 1e-8): sign-like, so an element whose gradient lies
+        # within fp32 noise of 0 moves by up to 2 lr either way (several steps average this out)
+        assert np.max(f_max) <= 1e-4 and np.max(fine) <= (1e-4 if n_steps > 1 else 1e-3) and flip_share <= 1e-5
+        assert np.abs(adv_n - r64["adv"].numpy()).max() <= 1e-5 and np.abs(ret - r64["ret"].numpy()).max() <= 1e-5
+        if name == "clip20":
+            ratio = r64["steps"][0]["ratio"].numpy()
+            out = float(((ratio < 0.8) | (ratio > 1.2)).mean())
+            print("clip20: %.0f %% of the first minibatch's ratios outside [0.8, 1.2]" % (100 * out))
+            assert 0.10 <= out <= 0.60 and recorded[0]["parts"][2] < 1.55
+        path = os.path.join(OUT, "solver_update_%s.npz" % name)
+        np.savez_compressed(path, **arrs)
+        print("   %s: %d bytes" % (os.path.basename(path), os.path.getsize(path)), flush=True)
+        assert os.path.getsize(path) < 1 << 20
+
+
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["kat", "bfs", "cones", "ppo", "nets", "env", "arch", "order"]
+    which = sys.argv[1:] or ["kat", "bfs", "cones", "ppo", "nets", "env", "arch", "order", "update"]
+    makers = {"kat": make_kat, "bfs": make_bfs, "cones": make_cones, "ppo": make_ppo,
+              "nets": make_nets, "env": make_env_traces, "arch": make_arch_update, "order": make_cone_order,
+              "update": make_solver_update}
     for w in which:
         print("==", w, flush=True)
-        {"kat": make_kat, "bfs": make_bfs, "cones": make_cones, "ppo": make_ppo,
-         "nets": make_nets, "env": make_env_traces, "arch": make_arch_update, "order": make_cone_order}[w]()
+        if w.startswith("update:"):  # update:g20,clip20 -- some cases only
+            make_solver_update(w[len("update:"):].split(","))
+        else:
+            makers[w]()

@@ -12,6 +12,7 @@ import torch
 import torch.nn.functional as F
 
 import golden_data as gd
+from mfma_forward import mfma_forward as _mfma_forward
 from heist_amd.agents import SolverAgent
 from heist_amd.networks import SolverNetwork
 
@@ -81,31 +82,6 @@ def test_fused_tail_forward_backward_matches_torch(gpu_device, R):
         if n.startswith(("conv", "fc_spatial")):
             worst = max(worst, _close(p.grad, q.grad, 1e-4, n))
     print("grid %s worst relative gradient difference %.3g" % (R, worst))
-
-
-def _mfma_forward(net, x):
-    """The fp32-MFMA forward through the C ABI (the passes _BackboneMFMA32 runs, deterministic):
-    the [n][R][C][P] activations a1, a2, a3."""
-    from heist_amd import _native as nat
-    from heist_amd.networks import _tc_act, _tc_queues
-    L, st, dev = nat.lib(), nat.stream(x.device), x.device
-    n, _, R, C = x.shape
-    P = lambda t: nat._vp(t.data_ptr())  # noqa: E731
-    q = _tc_queues(dev)
-    x4 = _tc_act(n, R, C, 3, dev)
-    s = x.stride()
-    nat.check(L.heist_train_obs_nhwc4(P(x), n, R, C, s[0], s[1], s[2], s[3], P(x4), st), "obs")
-    ys, xin = [], x4
-    for layer, m, ch in ((1, net.conv1, 32), (2, net.conv2, 64), (3, net.conv3, 64)):
-        f = torch.empty(L.heist_train_conv_frag_floats(layer, 0), device=dev)
-        nat.check(L.heist_train_conv_pack(layer, 0, P(m.weight.detach().contiguous()), P(f), st), "pack")
-        y = _tc_act(n, R, C, ch, dev)
-        nat.check(L.heist_train_conv(layer, 0, P(xin), n, R, C, P(f), P(m.bias.detach().contiguous()), None, P(y),
-                                     P(q), st), "conv")
-        ys.append(y[..., :ch].permute(0, 3, 1, 2))
-        xin = y
-    torch.cuda.synchronize(dev)
-    return ys
 
 
 def _ref64(net, x, U, masks=None):
@@ -261,7 +237,9 @@ def test_fused_tail_ppo_minibatch_golden_weights(gpu_device, path):
     """One PPO minibatch (agents/solver.py:172-199: zero-hidden forward, clipped loss,
     backward) of SolverAgent from the reference's seeded weights (nets.npz) on 2,048 states
     (the six golden inputs first): the loss parts and every parameter gradient, fused vs plain
-    torch fp32, within 1e-4 (relative to each gradient's max); then the clipped Adam step."""
+    torch fp32, within 1e-4 (relative to each gradient's max); then the clipped Adam step.
+    (GPU kernels against GPU torch on synthetic advantages; the same step and the whole update
+    against the reference's own numbers: tests/test_gpu_solver_update_golden.py.)"""
     z = gd.load("nets.npz")
     sd = {k[len("solver/"):]: torch.from_numpy(z[k]) for k in z.files if k.startswith("solver/")}
     ags = []

@@ -129,11 +129,14 @@ def test_c3_selfplay_4096_envs(gpu_device, tmp_path, precision):
     _roundtrip(tr, tmp_path)
 
 
-def test_c4_8192_envs_budget_40(gpu_device, tmp_path):
-    """BASELINE config 4 on one GPU: 8192 envs, the c4 curriculum at its top (budget 40)."""
+@pytest.mark.parametrize("precision", ["bf16", "fp32"])
+def test_c4_8192_envs_budget_40(gpu_device, tmp_path, precision):
+    """BASELINE config 4 on one GPU: 8192 envs, the c4 curriculum at its top (budget 40), on the
+    bf16 rollout kernels and on the fp32 rollout (the one bench.py's C4 training leg runs)."""
     n = 8192
     tr = _trainer(tmp_path, n, T=32, A=2, episode0=400, device=gpu_device, minibatch=16384,
-                  curriculum="c4", rollout_precision="bf16")
+                  curriculum="c4", rollout_precision=precision)
+    assert tr.solver.rollout_precision == precision
     assert tr.get_curriculum_phase(401)[1] == 40 and tr.CURRICULUM == CURRICULA["c4"]
     assert tr.env.max_cams == 13 and tr.env.max_guards == 8
     budgets = {tr.b_meta[e][1] for e in range(0, n, 97)}
