@@ -12,6 +12,14 @@ Fixture files (all numpy .npz, loaded with allow_pickle=False):
                   (environment.py:102-374): per-op reward (f64), done, status,
                   position, tick, camera headings, guard idx/headings,
                   visibility bits, state tensors for the first ops.
+  env_traces_offcorner.npz  (key `offcorner`) the same format on 16 traces whose start and
+                  vault are away from the grid corners: every lane of the observation's
+                  float4 under the vault, solver and vault in one float4, start == vault,
+                  the vault on the border ring, the start at (0, 0), assets named on the
+                  start and vault cells; actions steered towards the vault.
+  bfs_edges.npz   (key `bfs_edges`) bfs_path_exists on 64-wide / 64-high / thin grids:
+                  endpoints in the last row or column, walls under the endpoints,
+                  grid-filling corridors and their plugged twins, dense random fills.
   cones.npz       Camera.get_vision_cone_tiles / Guard.get_visible_tiles
                   sweeps (security.py:53-101, :161-192).
   cone_order.npz  the same methods' LIST order (first visit by ray index, then
@@ -179,7 +187,9 @@ def gen_ops(rng, n_ops, R, C):
     return ops
 
 
-def run_trace(cfg, layout, ops, n_state, budget):
+def run_trace(cfg, layout, ops, n_state, budget, policy=None):
+    """Replay ops through the reference env.  With a policy, op k is policy(env, k, ops[k]) (an
+    action chosen from the env's state as it stands before the op); rec["ops"] holds the ops run."""
     env = HeistEnvironment(cfg)
     env.budget.scale_budget(budget)
     walls, cams, guards = layout
@@ -187,9 +197,12 @@ def run_trace(cfg, layout, ops, n_state, budget):
     rec = {"valid": valid, "grid": env.grid.copy(), "n_walls": len(env.walls),
            "n_cams": len(env.cameras), "n_guards": len(env.guards), "spent": env.budget.spent,
            "reward": [], "done": [], "status": [], "pos": [], "tick": [], "cam_h": [],
-           "g_idx": [], "g_h": [], "vis": [], "state": []}
+           "g_idx": [], "g_h": [], "vis": [], "state": [], "ops": []}
     done = False
     for k, op in enumerate(ops):
+        if policy is not None:
+            op = policy(env, k, op)
+        rec["ops"].append(op)
         if op == -1:
             env.reset()
             r, d, st = 0.0, env.done, STATUS["reset"]
@@ -257,11 +270,8 @@ def make_env_traces():
     lay = synth_layout(rng, 24, 17, 25, n_cams=3, n_guards=2)
     cases.append(("synth24x17", 24, 17, 80, 25, lay, 300))
 
-    names, cfgs, valid, layouts, grids, nacc = [], [], [], [], [], []
-    ops_all, ops_off = [], [0]
-    out = {k: [] for k in ("reward", "done", "status", "pos", "tick", "cam_h", "g_idx", "g_h")}
-    vis_bits, state = [], []
     n_state = 24
+    runs = []
     for (name, R, C, ms, b, lay, n_ops) in cases:
         cfg = EnvironmentConfig(grid_rows=R, grid_cols=C, max_steps=ms, architect_budget=b)
         ops = gen_ops(rng, n_ops, R, C)
@@ -272,6 +282,19 @@ def make_env_traces():
         if name == "empty10":
             ops = [-1] + [2] * 7 + [4] * 7 + [3, -1] + ops[1:]
         rec = run_trace(cfg, lay, ops, n_state, b)
+        runs.append((name, cfg, b, lay, ops, rec))
+        print("trace %-20s %dx%d valid=%s cams=%d guards=%d ops=%d" % (name, R, C, rec["valid"], rec["n_cams"], rec["n_guards"], len(ops)), flush=True)
+    write_traces("env_traces.npz", runs, n_state)
+
+
+def write_traces(fname, runs, n_state):
+    """The env_traces.npz format from (name, cfg, budget, layout, ops, run_trace record) tuples."""
+    names, cfgs, valid, layouts, grids, nacc = [], [], [], [], [], []
+    ops_all, ops_off = [], [0]
+    out = {k: [] for k in ("reward", "done", "status", "pos", "tick", "cam_h", "g_idx", "g_h")}
+    vis_bits, state = [], []
+    for (name, cfg, b, lay, ops, rec) in runs:
+        R, C, ms = cfg.grid_rows, cfg.grid_cols, cfg.max_steps
         names.append(name)
         cfgs.append((R, C, ms, cfg.start_pos[0], cfg.start_pos[1], cfg.vault_pos[0], cfg.vault_pos[1], b))
         valid.append(rec["valid"]); layouts.append(lay); grids.append(rec["grid"].reshape(-1).astype(np.int8))
@@ -281,7 +304,6 @@ def make_env_traces():
             out[k].extend(rec[k])
         vis_bits.append(np.packbits(np.array(rec["vis"]).reshape(len(ops), -1), axis=1).reshape(-1))
         state.append(np.array(rec["state"], np.float32).reshape(-1))
-        print("trace %-20s %dx%d valid=%s cams=%d guards=%d ops=%d" % (name, R, C, rec["valid"], rec["n_cams"], rec["n_guards"], len(ops)), flush=True)
     arrs = pack_layouts(layouts)
     arrs.update(
         names=np.array(names), cfg=np.array(cfgs, np.int64), valid=np.array(valid, bool),
@@ -292,7 +314,107 @@ def make_env_traces():
         tick=np.array(out["tick"], np.int32), cam_h=np.array(out["cam_h"], np.float64),
         g_idx=np.array(out["g_idx"], np.int32), g_h=np.array(out["g_h"], np.float64),
         vis_bits=np.concatenate(vis_bits), state=np.concatenate(state), n_state=np.int64(n_state))
-    np.savez_compressed(os.path.join(OUT, "env_traces.npz"), **arrs)
+    np.savez_compressed(os.path.join(OUT, fname), **arrs)
+
+
+# ---------------------------------------------------------------------------
+# env traces with start and vault away from the grid corners
+# ---------------------------------------------------------------------------
+
+CHOOSE = 9  # an op the policy fills in
+
+# name: (R, C, max_steps, budget, start, vault, layout spec, forced first ops, n_ops, seed)
+# layout spec: None = empty, "list" = the placement-rule lists, else synth_layout keywords.
+# Vault lane = (vault_r * C + vault_c) & 3: the lane of the observation's float4 the vault is patched into.
+OFFCORNER_CASES = [
+    ("lane0_mid", 20, 20, 200, 15, (11, 13), (5, 8), {}, [], 120, 1),
+    ("lane1_bottom_left", 20, 20, 30, 20, (17, 2), (4, 9), {}, [], 120, 8002),
+    ("lane2_top_right", 20, 20, 200, 25, (2, 17), (14, 10), {}, [], 120, 2803),
+    ("lane3_adjacent", 20, 20, 200, 15, (8, 11), (7, 11), {}, [], 120, 4),
+    ("g32_lane0", 32, 32, 200, 40, (10, 20), (20, 12), {"n_cams": 4, "n_guards": 3}, [], 120, 605),
+    ("g32_lane3", 32, 32, 200, 40, (22, 14), (9, 23), {"n_cams": 4, "n_guards": 3}, [], 120, 6),
+    ("g13x17", 13, 17, 200, 20, (9, 3), (3, 12), {}, [], 120, 2407),
+    ("g16x20", 16, 20, 200, 20, (2, 14), (12, 5), {}, [], 120, 1108),
+    ("quad_from_left", 20, 20, 200, 15, (6, 8), (6, 9), None, [4], 60, 9),
+    ("quad_from_right", 20, 20, 200, 15, (9, 7), (9, 6), None, [3], 60, 10),
+    ("quad_from_above", 20, 20, 200, 15, (10, 4), (11, 4), None, [2], 60, 11),
+    ("quad_from_below", 20, 20, 200, 15, (5, 15), (4, 15), None, [1], 60, 12),
+    ("start_is_vault", 20, 20, 200, 15, (7, 6), (7, 6), {}, [], 40, 13),
+    ("vault_on_border", 20, 20, 200, 15, (15, 9), (19, 5), {}, [], 100, 14),
+    ("start_at_origin", 20, 20, 30, 15, (0, 0), (3, 2), {}, [], 80, 15),
+    ("placement_lists", 20, 20, 200, 40, (4, 7), (13, 10), "list", [], 100, 916),
+]
+
+
+def offcorner_layout(rng, R, C, budget, start, vault, spec):
+    if spec is None:
+        return [], [], []
+    if spec == "list":
+        # walls, cameras and guard patrol starts on the start and vault cells (refused for walls and
+        # cameras, environment.py:160-167; guards overwrite the tile, :148) and on (1, 1) and
+        # (R-2, C-2), which are ordinary cells here
+        walls = [start, vault, (1, 1), (5, 5), (9, 12), (1, 1), (0, 4)]
+        cams = [{"row": start[0], "col": start[1], "fov_angle": 60.0},
+                {"row": vault[0], "col": vault[1], "fov_angle": 90.0, "heading": 180.0},
+                {"row": R - 2, "col": C - 2, "fov_angle": 45.0, "heading": 225.0, "rotation_speed": 10.0},
+                {"row": 1, "col": 2, "fov_angle": 75.0, "heading": 90.0, "rotation_speed": 20.0, "vision_range": 5},
+                {"row": 1, "col": 1, "fov_angle": 60.0}]
+        guards = [{"patrol_path": [start, (start[0], start[1] - 1), (start[0] - 1, start[1] - 1)], "speed": 1,
+                   "vision_range": 2, "fov_angle": 60.0},
+                  {"patrol_path": [vault, (vault[0] + 1, vault[1]), (vault[0] + 2, vault[1])], "speed": 1,
+                   "vision_range": 2, "fov_angle": 60.0},
+                  {"patrol_path": [(1, 1), (2, 1)], "speed": 1, "vision_range": 3, "fov_angle": 90.0}]
+        return walls, cams, guards
+    return synth_layout(rng, R, C, budget, **spec)
+
+
+def offcorner_policy(rng, vault):
+    """Fixed ops stand; a CHOOSE op is, on a finished env, a reset() or (half the time) one more
+    step, else steered_action (golden_data.py)."""
+    sys.path.insert(0, os.path.dirname(OUT))
+    from golden_data import steered_action
+
+    def policy(env, k, op):
+        if op != CHOOSE:
+            return op
+        if env.done:
+            return -1 if rng.random() < 0.5 else int(rng.integers(0, 5))
+        return steered_action(rng, env.solver_pos, vault)
+    return policy
+
+
+def make_env_traces_offcorner():
+    n_state = 24
+    runs, seen = [], {}
+    for (name, R, C, ms, b, start, vault, spec, first, n_ops, seed) in OFFCORNER_CASES:
+        rng = np.random.default_rng(20261000 + seed)
+        lay = offcorner_layout(rng, R, C, b, start, vault, spec)
+        cfg = EnvironmentConfig(grid_rows=R, grid_cols=C, max_steps=ms, start_pos=start, vault_pos=vault,
+                                architect_budget=b)
+        assert n_ops <= 120
+        template = [-1] + first + [CHOOSE] * (n_ops - 1 - len(first))
+        rec = run_trace(cfg, lay, template, n_state, b, policy=offcorner_policy(rng, vault))
+        ops = rec["ops"]
+        st = np.array(rec["status"])
+        counts = {k: int((st == v).sum()) for k, v in STATUS.items()}
+        for k, v in counts.items():
+            if v:
+                seen.setdefault(k, []).append(name)
+        runs.append((name, cfg, b, lay, ops, rec))
+        print("trace %-18s %dx%d start=%s vault=%s lane=%d valid=%s walls=%d cams=%d guards=%d ops=%d | vault_reached %d "
+              "detected %d timeout %d already_done %d resets %d"
+              % (name, R, C, start, vault, (vault[0] * C + vault[1]) & 3, rec["valid"], rec["n_walls"], rec["n_cams"],
+                 rec["n_guards"], len(ops), counts["vault_reached"], counts["detected"], counts["timeout"],
+                 counts["already_done"], counts["reset"]), flush=True)
+        if rec["valid"] and start != vault and ms > 30:
+            assert counts["vault_reached"] >= 1, name + ": the vault was never reached, choose another seed"
+    for k in ("vault_reached", "detected", "timeout"):
+        print("status %-13s in %d traces: %s" % (k, len(seen.get(k, [])), " ".join(seen.get(k, []))), flush=True)
+        assert len(seen.get(k, [])) >= 2, k
+    write_traces("env_traces_offcorner.npz", runs, n_state)
+    size = os.path.getsize(os.path.join(OUT, "env_traces_offcorner.npz"))
+    print("env_traces_offcorner.npz: %d bytes" % size, flush=True)
+    assert size < 1 << 20
 
 
 # ---------------------------------------------------------------------------
@@ -397,6 +519,105 @@ def make_bfs():
         grids.append(g.reshape(-1).astype(np.int8))
         res.append(bfs_path_exists(g, start, goal))
     np.savez_compressed(os.path.join(OUT, "bfs.npz"), meta=np.array(meta, np.int64), grids=np.concatenate(grids), valid=np.array(res, bool))
+
+
+def serpentine(R, C, by_rows, far_end_first):
+    """Every odd line (row if by_rows, else column) but the last is a wall with one gap, at
+    alternating ends: one corridor that sweeps the whole grid.  Returns (grid, gap cells)."""
+    g = np.zeros((R, C) if by_rows else (C, R), np.int8)
+    n_lines, length = g.shape
+    gaps = []
+    for k, line in enumerate(range(1, n_lines - 1, 2)):
+        g[line, :] = TileType.WALL
+        at = length - 1 if (k % 2 == 0) == far_end_first else 0
+        g[line, at] = TileType.EMPTY
+        gaps.append((line, at) if by_rows else (at, line))
+    return (g if by_rows else np.ascontiguousarray(g.T)), gaps
+
+
+def make_bfs_edges():
+    """bfs_path_exists where bfs.npz does not go: 64-wide and 64-high grids (bit 63, lane 63), thin
+    grids, endpoints in the last row or column, wall tiles under the endpoints, corridors far
+    longer than 4 (R + C) and their plugged twins, dense random fills with nearby endpoints."""
+    rng = np.random.default_rng(23)
+    meta, grids, res, kinds = [], [], [], []
+
+    def add(kind, g, start, goal):
+        R, C = g.shape
+        meta.append((R, C, start[0], start[1], goal[0], goal[1]))
+        grids.append(g.reshape(-1).astype(np.int8))
+        res.append(bool(bfs_path_exists(g, tuple(start), tuple(goal))))
+        kinds.append(kind)
+
+    for (R, C) in ((64, 64), (33, 64), (3, 64), (64, 3)):
+        for by_rows in (True, False):
+            if (by_rows and R < 5) or (not by_rows and C < 5):
+                continue
+            for far in (True, False):
+                g, gaps = serpentine(R, C, by_rows, far)
+                # the corridor's two ends: the first line's closed end, the last line's far end
+                last = (R - 1) if by_rows else (C - 1)
+                n_gaps = len(gaps)
+                end_far = (n_gaps % 2 == 1) == far  # the side the last gap is on
+                if by_rows:
+                    a, b = (0, 0 if far else C - 1), (last, 0 if end_far else C - 1)
+                else:
+                    a, b = (0 if far else R - 1, 0), (0 if end_far else R - 1, last)
+                add("serpentine", g, a, b)
+                add("serpentine", g, b, a)
+                for _ in range(2):
+                    h = g.copy()
+                    h[gaps[int(rng.integers(0, n_gaps))]] = TileType.WALL
+                    s, t = (a, b) if rng.random() < 0.5 else (b, a)
+                    add("plugged", h, s, t)
+    n_serp = len(meta)
+    for i in range(152):
+        R, C = [(64, 64), (3, 64), (64, 3), (33, 64)][i % 4]
+        g = np.zeros((R, C), np.int8)
+        g[rng.random((R, C)) < rng.uniform(0.35, 0.45)] = TileType.WALL
+        other = rng.random((R, C)) < 0.03  # cameras, guards: walkable
+        g[other & (g == 0)] = rng.choice([TileType.CAMERA, TileType.GUARD])
+        if i % 3 == 0:  # an endpoint in the last row or column
+            start = (R - 1, int(rng.integers(0, C))) if i % 2 else (int(rng.integers(0, R)), C - 1)
+        else:
+            start = (int(rng.integers(0, R)), int(rng.integers(0, C)))
+        reach = int(rng.integers(1, 9))
+        goal = start
+        while goal == start:
+            goal = (int(np.clip(start[0] + rng.integers(-reach, reach + 1), 0, R - 1)),
+                    int(np.clip(start[1] + rng.integers(-reach, reach + 1), 0, C - 1)))
+        g[start] = TileType.START
+        g[goal] = TileType.VAULT
+        kind = "random"
+        if i % 10 == 3:
+            g[goal] = TileType.WALL
+            kind = "goal_wall"
+        elif i % 10 == 5:
+            g[start] = TileType.WALL  # the start tile itself is never checked
+            kind = "start_wall"
+        elif i % 10 == 7:
+            goal = start
+            g[start] = TileType.WALL if i % 20 == 7 else TileType.START
+            kind = "start_is_goal"
+        if i % 6 == 1:
+            start, goal = goal, start
+        add(kind, g, start, goal)
+    res_a = np.array(res, bool)
+    for k in sorted(set(kinds)):
+        sel = np.array([x == k for x in kinds])
+        print("bfs_edges %-14s %3d grids, %3d reachable" % (k, sel.sum(), res_a[sel].sum()), flush=True)
+    share = res_a.mean()
+    print("bfs_edges: %d grids (%d serpentine), reachable share %.2f" % (len(res), n_serp, share), flush=True)
+    assert 0.25 <= share <= 0.75
+    long_paths = 0
+    for (R, C, *_), k, v in zip(meta, kinds, res):
+        long_paths += int(k == "serpentine" and v and (R // 2) * C > 4 * (R + C) and (C // 2) * R > 4 * (R + C))
+    assert long_paths >= 8
+    assert all(res_a[np.array([x == "serpentine" for x in kinds])]) and not any(res_a[np.array([x == "plugged" for x in kinds])])
+    path = os.path.join(OUT, "bfs_edges.npz")
+    np.savez_compressed(path, meta=np.array(meta, np.int64), grids=np.concatenate(grids), valid=res_a)
+    print("bfs_edges.npz: %d bytes" % os.path.getsize(path), flush=True)
+    assert os.path.getsize(path) < 1 << 20
 
 
 # ---------------------------------------------------------------------------
@@ -843,10 +1064,11 @@ def make_solver_update(only=None):
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["kat", "bfs", "cones", "ppo", "nets", "env", "arch", "order", "update"]
+    which = sys.argv[1:] or ["kat", "bfs", "cones", "ppo", "nets", "env", "arch", "order", "update", "offcorner",
+                             "bfs_edges"]
     makers = {"kat": make_kat, "bfs": make_bfs, "cones": make_cones, "ppo": make_ppo,
               "nets": make_nets, "env": make_env_traces, "arch": make_arch_update, "order": make_cone_order,
-              "update": make_solver_update}
+              "update": make_solver_update, "offcorner": make_env_traces_offcorner, "bfs_edges": make_bfs_edges}
     for w in which:
         print("==", w, flush=True)
         if w.startswith("update:"):  # update:g20,clip20 -- some cases only

@@ -16,9 +16,21 @@ def load_json(name):
         return json.load(f)
 
 
-def env_traces():
+def steered_action(rng, pos, vault, p=0.7):
+    """The action rule of the off-corner traces and tests: with probability p a move that
+    reduces the Manhattan distance from pos to vault (uniform among those; actions are
+    0 stay, 1 up, 2 down, 3 left, 4 right), otherwise, or where no move does, uniform in 0..4."""
+    if rng.random() < p:
+        closer = [a for a, ok in ((1, pos[0] > vault[0]), (2, pos[0] < vault[0]), (3, pos[1] > vault[1]),
+                                  (4, pos[1] < vault[1])) if ok]
+        if closer:
+            return int(closer[int(rng.integers(0, len(closer)))])
+    return int(rng.integers(0, 5))
+
+
+def env_traces(fname="env_traces.npz"):
     """Yield one dict per recorded trace (layout in the reference's list/dict form)."""
-    z = load("env_traces.npz")
+    z = load(fname)
     cfg = z["cfg"]
     n = len(cfg)
     grid_off = 0
@@ -94,8 +106,8 @@ def cone_orders():
                    heading=float(head), walls=walls, order=order)
 
 
-def bfs_cases():
-    z = load("bfs.npz")
+def bfs_cases(fname="bfs.npz"):
+    z = load(fname)
     cur = 0
     for (R, C, sr, sc, gr, gc), v in zip(z["meta"], z["valid"]):
         g = z["grids"][cur:cur + R * C].reshape(R, C)

@@ -11,18 +11,12 @@ import pytest
 import torch
 
 import golden_data as gd
+from env_parity import check_golden_trace
 from oracle import pyoracle as po
 from heist_amd import EnvironmentConfig, HeistEnv
 from heist_amd.layouts import synthetic_layouts, valid_synthetic_layouts
 
 pytestmark = pytest.mark.gpu
-
-STATUS_RESET = 5
-
-
-def _cfg(tr):
-    return EnvironmentConfig(grid_rows=tr["R"], grid_cols=tr["C"], max_steps=tr["max_steps"], start_pos=tr["start"],
-                             vault_pos=tr["vault"], architect_budget=tr["budget"])
 
 
 @pytest.mark.parametrize("path", ["step_kernel", "lean_k1"])
@@ -31,46 +25,9 @@ def _cfg(tr):
 def test_golden_trace_bit_exact(tr, cones, path, gpu_device, monkeypatch):
     """Every golden trace on both single-tick paths: the step kernel (HEIST_STEP_LEAN=0) and,
     where the lean K-tick kernel serves the grid (20 x 20 at one wave per env, 32 x 32),
-    heist_step as a one-tick heist_step_multi launch (the training rollout's tick)."""
-    if path == "lean_k1":
-        monkeypatch.setenv("HEIST_MULTI_WAVES", "1")
-        monkeypatch.setenv("HEIST_STEP_LEAN", "1")
-    else:
-        monkeypatch.setenv("HEIST_STEP_LEAN", "0")
-    env = HeistEnv(1, _cfg(tr), max_cams=16, max_guards=8, max_path=64, device=gpu_device, auto_reset=False)
-    lean_grid = (tr["R"], tr["C"]) in ((20, 20), (32, 32))
-    assert env.kernel_config()["step_lean"] == (1 if path == "lean_k1" and lean_grid else 0)
-    env.set_guard_cones(cones)
-    valid = env.set_layouts([(tr["walls"], tr["cams"], tr["guards"])], budget=tr["budget"])
-    assert bool(valid[0]) == tr["valid"]
-    st = env.export(grid=True)
-    np.testing.assert_array_equal(st["grid"][0].cpu().numpy(), tr["grid"])
-    acc = [int(st[k][0]) for k in ("n_walls", "n_cams", "n_guards", "spent")]
-    assert acc == tr["accepted"]
-    nc, ng = tr["accepted"][1], tr["accepted"][2]
-    for k, op in enumerate(tr["ops"]):
-        ctx = "%s op#%d" % (tr["name"], k)
-        if op == -1:
-            obs = env.reset()
-            r, d, s = 0.0, None, STATUS_RESET
-        else:
-            obs, _, dn, stt = env.step(torch.tensor([op]))
-            r, d, s = float(env.reward64[0]), bool(dn[0]), int(stt[0])
-        st = env.export()
-        assert r == tr["reward"][k], ctx
-        if d is not None:
-            assert d == tr["done"][k], ctx
-        assert s == tr["status"][k], ctx
-        assert (int(st["pos_r"][0]), int(st["pos_c"][0])) == tuple(tr["pos"][k]), ctx
-        assert int(st["tick"][0]) == tr["tick"][k], ctx
-        assert bool(st["done"][0]) == tr["done"][k], ctx
-        np.testing.assert_array_equal(st["cam_heading"][0, :nc].cpu().numpy(), tr["cam_h"][k], err_msg=ctx)
-        np.testing.assert_array_equal(st["guard_idx"][0, :ng].cpu().numpy(), tr["g_idx"][k], err_msg=ctx)
-        np.testing.assert_array_equal(st["guard_heading"][0, :ng].cpu().numpy(), tr["g_h"][k], err_msg=ctx)
-        o = obs[0].cpu().numpy()
-        np.testing.assert_array_equal(o[1] > 0.5, tr["vis"][k], err_msg=ctx)
-        if k < len(tr["state"]):
-            assert o.tobytes() == tr["state"][k].tobytes(), ctx
+    heist_step as a one-tick heist_step_multi launch (the training rollout's tick).  The body is
+    env_parity.check_golden_trace, shared with test_gpu_env_offcorner.py."""
+    check_golden_trace(tr, cones, path, gpu_device, monkeypatch)
 
 
 def test_cones_bit_exact(gpu_device):

@@ -11,6 +11,7 @@ import golden_data as gd
 from oracle import pyoracle as po
 
 STATUS_RESET = 5
+OFFCORNER = "env_traces_offcorner.npz"  # start and vault away from the grid corners
 
 
 def _replay(tr):
@@ -19,7 +20,7 @@ def _replay(tr):
     return env, valid
 
 
-@pytest.mark.parametrize("tr", list(gd.env_traces()), ids=lambda t: t["name"])
+@pytest.mark.parametrize("tr", list(gd.env_traces()) + list(gd.env_traces(OFFCORNER)), ids=lambda t: t["name"])
 def test_env_trace_bit_exact(tr):
     env, valid = _replay(tr)
     assert valid == tr["valid"]
@@ -80,6 +81,49 @@ def test_bfs_matches_reference():
         assert po.bfs(c["grid"], c["start"], c["goal"]) == c["valid"]
         n += 1
     assert n >= 1000
+
+
+def test_offcorner_fixture_covers_its_cases():
+    """What make_env_traces_offcorner asserted when it wrote the file, from the file: every
+    vault lane (the float4 lane of channel 2 the vault is patched into) at 20 x 20, lanes 0 and
+    3 at 32 x 32, a width that is no multiple of 4, each finishing status in at least two
+    traces, the vault reached wherever it can be, and the four same-quad approaches."""
+    trs = list(gd.env_traces(OFFCORNER))
+    assert 14 <= len(trs) and all(len(t["ops"]) <= 120 for t in trs)
+    lanes = lambda R: {(t["vault"][0] * t["C"] + t["vault"][1]) & 3 for t in trs  # noqa: E731
+                       if (t["R"], t["C"]) == (R, R) and t["valid"] and t["start"] != t["vault"]}
+    assert lanes(20) == {0, 1, 2, 3} and {0, 3} <= lanes(32)
+    assert {(13, 17), (16, 20)} <= {(t["R"], t["C"]) for t in trs}
+    for t in trs:
+        assert t["start"] != (1, 1) and t["vault"] != (t["R"] - 2, t["C"] - 2), t["name"]
+    for code in (1, 2, 3):  # detected, vault_reached, timeout
+        assert sum(bool((t["status"] == code).any()) for t in trs) >= 2, po.STATUS_NAMES[code]
+    short = [t for t in trs if t["max_steps"] <= 30]
+    assert len(short) == 2
+    for t in trs:
+        if t["valid"] and t["start"] != t["vault"] and t["max_steps"] > 30:
+            assert (t["status"] == 2).any(), t["name"]
+    quad = [t for t in trs if t["name"].startswith("quad_from_")]
+    steps = set()
+    for t in quad:  # the first op walks onto the vault from a neighbouring cell
+        assert t["status"][1] == 2 and tuple(t["pos"][1]) == t["vault"], t["name"]
+        steps.add((t["vault"][0] - t["start"][0], t["vault"][1] - t["start"][1]))
+    assert steps == {(0, 1), (0, -1), (1, 0), (-1, 0)}
+    assert len({(t["vault"][0] * t["C"] + t["vault"][1]) & 3 for t in quad}) == 4
+    names = {t["name"] for t in trs}
+    assert {"start_is_vault", "vault_on_border", "start_at_origin", "placement_lists"} <= names
+
+
+def test_bfs_edges_match_reference():
+    """bfs_edges.npz: grids up to 64 x 64 and down to 3 wide, endpoints in the last row or
+    column and on wall tiles, grid-filling corridors and their plugged twins."""
+    cases = list(gd.bfs_cases("bfs_edges.npz"))
+    for c in cases:
+        assert po.bfs(c["grid"], c["start"], c["goal"]) == c["valid"], (c["grid"].shape, c["start"], c["goal"])
+    share = np.mean([c["valid"] for c in cases])
+    assert len(cases) >= 190 and 0.25 <= share <= 0.75
+    assert {c["grid"].shape for c in cases} == {(64, 64), (3, 64), (64, 3), (33, 64)}
+    assert any(63 in c["start"] or 63 in c["goal"] for c in cases)
 
 
 def test_gae_matches_reference():
