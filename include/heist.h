@@ -195,6 +195,26 @@ int heist_obs_expand(const uint32_t* records, int64_t n_records, const int32_t* 
                      const int8_t* grid, int n_envs, int rows, int cols, int vault_r, int vault_c, float* obs_out,
                      heist_stream_t stream);
 
+/* heist_step_multi with the compact record of every row in place of the row itself, no reference
+ * counterpart as an entry point (action replay, search from forked states, offline datasets: K
+ * ticks of N envs are K N records, 64 B each at 20 x 20, instead of K N rows of 4,800 B).
+ *   records_out [K][N][W] uint32, W = heist_obs_record_bytes(rows, cols) / 4, 16-byte aligned:
+ *   records_out[k][e] equals, byte for byte, what heist_obs_pack gives for row [k][e] of the
+ *   heist_step_multi launch with the same arguments; reward_out, reward64_out, done_out and
+ *   status_out are bit-identical to that launch's and the handle ends in the same state.
+ * heist_step_records_direct: 1 when the K-tick kernel writes the records itself (the lean or the
+ *   generic K-tick kernel serves the handle and no stamps are armed: no observation row is
+ *   written anywhere and obs_scratch is not touched), 0 when the fallback runs, -1 on a bad handle.
+ * Fallback (no K-tick kernel for the grid, e.g. cols not a multiple of 4, or sample counters,
+ *   stamps or a probe mode armed): K times heist_step into obs_scratch [N][3][R][C] float32 and
+ *   heist_obs_pack of it, on `stream`; obs_scratch may be NULL only on the direct route.
+ * HEIST_EINVAL: K outside 1..1024, a NULL actions, records_out, reward_out, done_out or
+ * status_out, records_out not 16-byte aligned, obs_scratch NULL when the fallback is needed. */
+int heist_step_records_direct(heist_t h);
+int heist_step_multi_records(heist_t h, int K, const int64_t* actions, uint32_t* records_out, float* reward_out,
+                             double* reward64_out, uint8_t* done_out, int8_t* status_out, int auto_reset,
+                             float* obs_scratch, heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

@@ -26,6 +26,9 @@ hipError_t launch_step(const EnvParams& p, const int64_t* actions, float* obs, f
 hipError_t launch_step_multi(const EnvParams& p, int K, const int64_t* actions, float* obs,
                              float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
                              hipStream_t st);
+hipError_t launch_step_multi_records(const EnvParams& p, int K, const int64_t* actions, uint32_t* records,
+                                     float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
+                                     hipStream_t st);
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,
                          double* guard_heading, hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
@@ -188,6 +191,59 @@ std::vector<double> heading_table(int R, int C) {
 bool lean_serves(const heist_env* h) {
   const heist::MultiRoute r = heist::multi_route(h->p);
   return h->step_lean && r.kind == heist::MultiRoute::kLean && !r.stamped;
+}
+
+// heist_step_multi_records writes its records from the K-tick kernel itself: the lean or the
+// generic K-tick kernel takes the launch (not K single ticks, not a probe variant) unstamped
+bool records_direct(const heist_env* h) {
+  const heist::MultiRoute r = heist::multi_route(h->p);
+  return (r.kind == heist::MultiRoute::kLean || r.kind == heist::MultiRoute::kGeneric) && !r.stamped;
+}
+
+// A K-tick launch on h with the shared fan table's bookkeeping (heist_step_multi and
+// heist_step_multi_records): the table (FanTick) is refilled when stale, used up, or last used by
+// a launch on another stream (streams do not order a refill against a launch still reading the
+// table: the new stream waits, on the device, for the event recorded behind the last K-tick
+// launch), else read at the launch's offset -- only when a K-tick kernel that reads the table
+// runs (otherwise K single ticks advance the headings).  launch(q) issues the kernels on st with
+// the launch's EnvParams.
+template <class Launch>
+int fan_table_launch(heist_env* h, int K, hipStream_t st, const char* what, Launch launch) {
+  const std::string w(what);
+  EnvParams q = h->p;
+  const heist::MultiRoute route = heist::multi_route(q);
+  const bool kt = route.kind == heist::MultiRoute::kGeneric || route.kind == heist::MultiRoute::kLean;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  int next_pos = -1;
+  if (kt && q.fan_on) {
+    int pos = h->fan_pos;
+    if (pos < 0 || pos + K > heist::kFanTicks || st != h->fan_stream) {
+      if (h->fan_used && st != h->fan_stream)  // the refill must not overtake a launch still reading the table
+        if (int rc = check_hip(hipStreamWaitEvent(st, h->fan_done, 0), (w + ": previous stream").c_str())) return rc;
+      q.fan_fill = 1;
+      pos = 0;
+    }
+    q.fan_base = pos;
+    next_pos = pos + K;
+  }
+  const int rc = check_hip(launch(q), what);
+  // the table position advances only with a launch that was issued
+  h->fan_pos = rc ? -1 : next_pos;
+  if (!rc && kt && q.fan_on) {
+    if (!h->fan_done)
+      if (int e = check_hip(hipEventCreateWithFlags(&h->fan_done, hipEventDisableTiming), (w + ": event").c_str())) {
+        h->fan_pos = -1;
+        return e;
+      }
+    if (int e = check_hip(hipEventRecord(h->fan_done, st), (w + ": event record").c_str())) {
+      h->fan_pos = -1;
+      return e;
+    }
+    h->fan_stream = st;
+    h->fan_used = true;
+  }
+  return rc;
 }
 
 }  // namespace
@@ -436,48 +492,51 @@ int heist_step_multi(heist_t h, int K, const int64_t* actions, float* obs_out, f
   // (without a K-tick variant the launch runs K single ticks: either kernel's size may apply)
   HEIST_REQUIRE(!h->p.stamps || h->stamp_words >= std::max(heist_stamp_words(h, 1), heist_stamp_words(h, 0)),
                 "heist_step_multi: stamp buffer too small");
+  return fan_table_launch(h, K, (hipStream_t)stream, "heist_step_multi", [&](const EnvParams& q) {
+    return heist::launch_step_multi(q, K, actions, obs_out, reward_out, reward64_out, done_out, status_out, auto_reset,
+                                    (hipStream_t)stream);
+  });
+}
+
+int heist_step_records_direct(heist_t h) {
+  if (check_handle(h)) return -1;
+  return records_direct(h) ? 1 : 0;
+}
+
+int heist_step_multi_records(heist_t h, int K, const int64_t* actions, uint32_t* records_out, float* reward_out,
+                             double* reward64_out, uint8_t* done_out, int8_t* status_out, int auto_reset,
+                             float* obs_scratch, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(K >= 1 && K <= 1024, "heist_step_multi_records: need 1 <= K <= 1024");
+  HEIST_REQUIRE(actions && records_out && reward_out && done_out && status_out,
+                "heist_step_multi_records: null output/input");
+  HEIST_REQUIRE(((uintptr_t)records_out & 15) == 0, "heist_step_multi_records: records_out must be 16-byte aligned");
   hipStream_t st = (hipStream_t)stream;
-  // the shared fan table (FanTick): refilled when stale, used up, or last used by a launch on
-  // another stream (streams do not order a refill against a launch still reading the table:
-  // the new stream waits, on the device, for the event recorded behind the last K-tick
-  // launch), else read at the launch's offset -- only when a K-tick kernel that reads the table
-  // runs (otherwise K single ticks advance the headings)
-  EnvParams q = h->p;
-  const heist::MultiRoute route = heist::multi_route(q);
-  const bool kt = route.kind == heist::MultiRoute::kGeneric || route.kind == heist::MultiRoute::kLean;
-  q.fan_fill = 0;
-  q.fan_base = 0;
-  int next_pos = -1;
-  if (kt && q.fan_on) {
-    int pos = h->fan_pos;
-    if (pos < 0 || pos + K > heist::kFanTicks || st != h->fan_stream) {
-      if (h->fan_used && st != h->fan_stream)  // the refill must not overtake a launch still reading the table
-        if (int rc = check_hip(hipStreamWaitEvent(st, h->fan_done, 0), "heist_step_multi: previous stream")) return rc;
-      q.fan_fill = 1;
-      pos = 0;
-    }
-    q.fan_base = pos;
-    next_pos = pos + K;
+  if (records_direct(h))
+    return fan_table_launch(h, K, st, "heist_step_multi_records", [&](const EnvParams& q) {
+      return heist::launch_step_multi_records(q, K, actions, records_out, reward_out, reward64_out, done_out,
+                                              status_out, auto_reset, st);
+    });
+  // the fallback: K single ticks, each packed from the scratch rows (stream order keeps tick k's
+  // pack ahead of tick k + 1's step)
+  HEIST_REQUIRE(obs_scratch != nullptr, "heist_step_multi_records: obs_scratch is null and the handle needs it "
+                                        "(heist_step_records_direct is 0)");
+  HEIST_REQUIRE(!h->p.stamps || h->stamp_words >= heist_stamp_words(h, 0),
+                "heist_step_multi_records: stamp buffer too small");
+  const EnvParams& p = h->p;
+  const size_t n = (size_t)p.n_envs, W = (size_t)heist::obs_record_words(p.R, p.C);
+  h->fan_pos = -1;  // headings advanced outside the K-tick launches' accounting
+  for (int k = 0; k < K; ++k) {
+    if (int rc = check_hip(heist::launch_step(p, actions + k * n, obs_scratch, reward_out + k * n,
+                                              reward64_out ? reward64_out + k * n : nullptr, done_out + k * n,
+                                              status_out + k * n, auto_reset, st),
+                           "heist_step_multi_records: step"))
+      return rc;
+    if (int rc = check_hip(heist::launch_obs_pack(obs_scratch, (int64_t)n, p.R, p.C, p.vr, p.vc, records_out + k * n * W, st),
+                           "heist_step_multi_records: pack"))
+      return rc;
   }
-  const int rc = check_hip(heist::launch_step_multi(q, K, actions, obs_out, reward_out, reward64_out, done_out,
-                                                    status_out, auto_reset, st),
-                           "heist_step_multi");
-  // the table position advances only with a launch that was issued
-  h->fan_pos = rc ? -1 : next_pos;
-  if (!rc && kt && q.fan_on) {
-    if (!h->fan_done)
-      if (int e = check_hip(hipEventCreateWithFlags(&h->fan_done, hipEventDisableTiming), "heist_step_multi: event")) {
-        h->fan_pos = -1;
-        return e;
-      }
-    if (int e = check_hip(hipEventRecord(h->fan_done, st), "heist_step_multi: event record")) {
-      h->fan_pos = -1;
-      return e;
-    }
-    h->fan_stream = st;
-    h->fan_used = true;
-  }
-  return rc;
+  return 0;
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

@@ -17,6 +17,7 @@
 // of the K-tick and lean kernels (kStepOcc / multi_occ, step_lean_kernel), the knobs for
 // block b = env b, the snake draft and wave priority by cost rank (block_env, order_kernel),
 // the unpacked dedup flush at two waves (cast_rays), the lean kernel's probe modes 21-28.
+#include <type_traits>
 #include <utility>
 
 #include "heist_device.h"
@@ -692,12 +693,14 @@ __device__ void cast_rays(unsigned char* smem, const EnvLds& L, int mode, int pr
             if (b0 + lane < nt && qn + b0 + lane < 64) queue[qn + b0 + lane] = (k << 16) | (int)fan->tie[b0 + lane];
           qn += nt;
           // directions 0 .. 63 from the registers loaded with the header (a lane permute),
-          // the rest of a wide fan from the table
+          // the rest of a wide fan from the table.  Every lane takes part in the permute: a
+          // packed march mixes both kinds (pairs of two members), and a lane that sat the
+          // permute out would hand a zero direction to the lanes that read from it
           const float* fu = fan->uniq;
           march_uniq(k, fh.n_uniq, [&](int j) {
-            if (j < 64)
-              return make_float2(__shfl(fh.dir.x, j, 64), __shfl(fh.dir.y, j, 64));
-            return make_float2(fu[2 * j], fu[2 * j + 1]);
+            float2 d = make_float2(__shfl(fh.dir.x, j & 63, 64), __shfl(fh.dir.y, j & 63, 64));
+            if (j >= 64) d = make_float2(fu[2 * j], fu[2 * j + 1]);
+            return d;
           });
         }
         continue;
@@ -1801,6 +1804,68 @@ __device__ __forceinline__ void stamp_guard_cones(const EnvLds& L, uint8_t* gvis
   }
 }
 
+// Record output (REC) of the K-tick kernels: a tick's row is the compact record of
+// heist_obs.hip (heist_obs_pack's, byte for byte) instead of the [3][R][C] floats -- nvis =
+// ceil(R C / 32) visibility words (cell i is bit i & 31 of word i >> 5), the position word
+// row | col << 8 and zero words up to a multiple of four.  The solver's cell is the one cell of
+// channel 2 above 0.5 unless it stands on the vault, and then obs_pack names the vault: the
+// position word is the solver's cell either way.  The pointer the kernels call `obs` is then the
+// uint32 record array [K][N][W].
+template <bool REC>
+using obs_out_t = std::conditional_t<REC, uint32_t, float>;
+
+// The visibility nibble of a channel-1 quad (4 bytes, each 0 or 1; byte i -> bit i): the
+// products' cross terms land on bits 7, 14, 15, 21, 22, 23, below the nibble and apart, so no
+// carry reaches it.
+__device__ __forceinline__ uint32_t vis_nibble(uint32_t v) { return (v * 0x10204080u) >> 28; }
+
+// The OR of w over each aligned group of 8 lanes, in the group's lane 0 (obs_pack_kernel's three
+// __shfl_xor as DPP moves: no LDS round trip, no lane-address registers): lanes ^ 1, lanes ^ 2,
+// then the mirror of the 8 lanes, whose quads by then hold one value each.
+__device__ __forceinline__ uint32_t or8_lanes(uint32_t w) {
+  w |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w, 0xB1, 0xf, 0xf, true);   // quad_perm [1, 0, 3, 2]
+  w |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w, 0x4E, 0xf, 0xf, true);   // quad_perm [2, 3, 0, 1]
+  w |= (uint32_t)__builtin_amdgcn_update_dpp(0, (int)w, 0x141, 0xf, 0xf, true);  // row_half_mirror
+  return w;
+}
+
+// A tick's record by the observation lanes (step_multi_body<.., REC>): one lane per visibility
+// word, from the word's 8 quads of ray plane | guard plane (a word spans grid rows when C < 32:
+// each quad has its own (r, c0), as in write_obs_ch1_tail; quads past R C / 4 add nothing), and
+// the first W - nvis lanes the position word and the pad.
+template <int NT>
+__device__ __forceinline__ void write_record(const EnvParams& p, const EnvScalars& s, const EnvLds& L,
+                                             const uint8_t* gvis, uint32_t* __restrict__ o) {
+  constexpr int PW = ObsLanes<NT>::PW;
+  const int t = (int)threadIdx.x - ObsLanes<NT>::LB;
+  if (t < 0) return;
+  const int n4 = p.RC / 4, c4 = p.C / 4, nvis = (p.RC + 31) >> 5, W = (nvis + 4) & ~3;
+  const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o, (short)0, 4 * W, 0x00020000);
+  for (int w = t; w < nvis; w += PW) {
+    uint32_t word = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int q = 8 * w + i;
+      if (q >= n4) break;
+      const int r = q / c4, c0 = 4 * (q - r * c4);
+      const int a = L.at(r, c0);
+      uint32_t v;
+      if ((kRing & 3) == 0) {
+        v = *reinterpret_cast<const uint32_t*>(L.vis + a) | *reinterpret_cast<const uint32_t*>(gvis + a);
+      } else {
+        const uint16_t* vp2 = reinterpret_cast<const uint16_t*>(L.vis + a);
+        const uint16_t* gp2 = reinterpret_cast<const uint16_t*>(gvis + a);
+        v = ((uint32_t)vp2[0] | ((uint32_t)vp2[1] << 16)) | ((uint32_t)gp2[0] | ((uint32_t)gp2[1] << 16));
+      }
+      word |= vis_nibble(v) << (4 * i);
+    }
+    __builtin_amdgcn_raw_buffer_store_b32(word, rs, 4 * w, 0, 0);
+  }
+  if (t < W - nvis)
+    __builtin_amdgcn_raw_buffer_store_b32(t == 0 ? (uint32_t)s.pos_r | ((uint32_t)s.pos_c << 8) : 0u, rs,
+                                          4 * (nvis + t), 0, 0);
+}
+
 // K consecutive heist_step ticks of one env per workgroup (environment.py:216-299 and
 // :347-374 K times), with actions[k][env] known up front: what env-only throughput and
 // action replay need.  The per-env state stays on chip for the whole launch -- grid, stop
@@ -1828,13 +1893,16 @@ __device__ __forceinline__ void stamp_guard_cones(const EnvLds& L, uint8_t* gvis
 // PROBE (profiling variant, HEIST_PROBE_MODE at heist_create; results wrong on purpose):
 // bit 0 skips the raycast and the cone stamps, bit 1 the observation stores, bit 2 the
 // rays' marches (directions and tie screens only).
-template <int W, int D, bool STAMP = false, int PROBE = 0>
+// REC (plain instances only): the tick's row is its compact record (write_record): no static
+// channels, no solver quad.
+template <int W, int D, bool STAMP = false, int PROBE = 0, bool REC = false>
 __device__ __forceinline__ void step_multi_body(
-    const EnvParams& p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
+    const EnvParams& p, int K, const int64_t* __restrict__ actions, obs_out_t<REC>* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset,
     unsigned char* smem, int e) {
   constexpr int NT = 64 * W;
   constexpr bool SOLO = W == 1;  // one wave does every role
+  static_assert(!REC || (!STAMP && PROBE == 0), "record output: the plain instances only");
   const int t = threadIdx.x;
   const bool w0 = (t >> 6) == 0;
   const int RC = p.RC, N = p.n_envs;
@@ -1885,7 +1953,7 @@ __device__ __forceinline__ void step_multi_body(
   const bool live_cam = t < s.n_cams, live_guard = g >= 0 && g < s.n_guards;
   bool cached = false;
   // one wave per env: the observation's per-launch constants in registers (ObsRegs)
-  const bool reg_obs = SOLO && p.RC <= 256 * kObsQ;
+  const bool reg_obs = !REC && SOLO && p.RC <= 256 * kObsQ;
   ObsRegs obr;
   // a cached guard's cone entry for the coming tick, loaded one tick ahead: the pose after
   // its move (idx + step, nslot) if the env acts and the patrol has >= 2 points
@@ -1912,7 +1980,8 @@ __device__ __forceinline__ void step_multi_body(
     dst[1] = cb;
   };
   __syncthreads();  // records in LDS
-  if (SOLO && reg_obs) obs_regs_init(p, L, obr);
+  if constexpr (!REC)
+    if (SOLO && reg_obs) obs_regs_init(p, L, obr);
   if (live_guard) {
     const Guard gd = as_guard(rec[t]);
     cached = gd.hslot != kUncached;
@@ -1997,11 +2066,13 @@ __device__ __forceinline__ void step_multi_body(
         HEIST_MULTI_STAMP(1);  // 1: emitter update
         publish_emitters(L, E, n_slot);
       }
-      if (!(PROBE & 2)) {
-        if (SOLO && reg_obs)
-          write_obs_regs<true>(p, s, L, gvis, obr, obs + ((size_t)k * N + e) * 3 * RC);
-        else
-          write_obs_static_lds<NT>(p, L, plane, obs + ((size_t)k * N + e) * 3 * RC);
+      if constexpr (!REC) {
+        if (!(PROBE & 2)) {
+          if (SOLO && reg_obs)
+            write_obs_regs<true>(p, s, L, gvis, obr, obs + ((size_t)k * N + e) * 3 * RC);
+          else
+            write_obs_static_lds<NT>(p, L, plane, obs + ((size_t)k * N + e) * 3 * RC);
+        }
       }
       clear_planes<NT>(p, L, gvis, true);
     } else {  // the emitters with every guard back at patrol point 0, headings kept
@@ -2111,7 +2182,9 @@ __device__ __forceinline__ void step_multi_body(
         status_out[ko] = (int8_t)status;
       }
     }
-    if (!(PROBE & 2)) {
+    if constexpr (REC) {
+      write_record<NT>(p, s, L, gvis, obs + ((size_t)k * N + e) * (size_t)(((((RC + 31) >> 5) + 4) & ~3)));
+    } else if (!(PROBE & 2)) {
       if (SOLO && reg_obs)
         write_obs_regs<false>(p, s, L, gvis, obr, obs + ((size_t)k * N + e) * 3 * RC);
       else
@@ -2147,13 +2220,13 @@ __device__ __forceinline__ void step_multi_body(
   }
 }
 
-template <int W, int D, bool STAMP = false, int PROBE = 0>
+template <int W, int D, bool STAMP = false, int PROBE = 0, bool REC = false>
 __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(multi_occ(W)))) void step_multi_kernel(
-    EnvParams p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
+    EnvParams p, int K, const int64_t* __restrict__ actions, obs_out_t<REC>* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = block_env(p);
-  step_multi_body<W, D, STAMP, PROBE>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
+  step_multi_body<W, D, STAMP, PROBE, REC>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
 }
 
 // ---------------------------------------------------------------------------
@@ -2344,7 +2417,8 @@ static size_t lean_lds_bytes(const EnvParams& p, int K) {
 // The lean tick issues its stores every tick after the LDS-DMA of the next tick's data:
 // observation channels 0, 1, 2 for Q quads per lane (3 Q), reward, reward64, done, status.
 // The next tick's `s_waitcnt vmcnt(3 Q + 4)` (kStores) therefore retires the DMA and never
-// waits for a store.
+// waits for a store.  The record form (REC) issues Q record-word stores and the position / pad
+// store in place of the 3 Q observation stores: Q + 1 + 4.
 
 // A cached guard's per-tick state packed in two registers: patrol index | step << 8 | len
 // << 16 | heading slot << 24, and position | position 0 << 16 (row | col << 8 each); the slot
@@ -2363,13 +2437,13 @@ struct LeanGuard {
 // inlined: the lean loop is then scheduled and register-allocated on its own (C2 5.78 ->
 // 5.64-5.71 us per tick; with the body removed altogether 5.66-5.69, profiles/r05as_*), at
 // the price of a call frame (scratch) on the rare generic path.
-template <int D>
+template <int D, bool REC>
 __device__ __attribute__((noinline)) void lean_generic_body(EnvParams p, int K, const int64_t* __restrict__ actions,
-                                                            float* __restrict__ obs, float* __restrict__ rew,
+                                                            obs_out_t<REC>* __restrict__ obs, float* __restrict__ rew,
                                                             double* __restrict__ rew64, uint8_t* __restrict__ done_out,
                                                             int8_t* __restrict__ status_out, int auto_reset,
                                                             unsigned char* smem, int e) {
-  step_multi_body<1, D, false, 0>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
+  step_multi_body<1, D, false, 0, REC>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
 }
 
 // STAMP (instrumentation, heist_step_stamps armed): lane 0 sums the shader clock spent in 9
@@ -2380,9 +2454,11 @@ __device__ __attribute__((noinline)) void lean_generic_body(EnvParams p, int K, 
 // spilled instead of 23, slower everywhere) and removed (DESIGN.md §10 item 4,
 // profiles/r06zc_occ5_env_configs.log).  The kernel's profiling instances (probe modes 21-28,
 // the removal ladder of DESIGN.md §6.3) were measured and removed too (profiles/r05t_lean_ab.log).
-template <int R_, int C_, bool STAMP = false, int NW = 1>
+// REC (plain instances only): the tick's row is its compact record (obs_out_t); only the store
+// block (6.) differs.
+template <int R_, int C_, bool STAMP = false, int NW = 1, bool REC = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) void step_lean_kernel(
-    EnvParams p, int K, const int64_t* __restrict__ actions, float* __restrict__ obs, float* __restrict__ rew,
+    EnvParams p, int K, const int64_t* __restrict__ actions, obs_out_t<REC>* __restrict__ obs, float* __restrict__ rew,
     double* __restrict__ rew64, uint8_t* __restrict__ done_out, int8_t* __restrict__ status_out, int auto_reset) {
   constexpr int D = lean_gap(R_, C_);
   constexpr int PC = C_ + 2 * kRing;
@@ -2395,7 +2471,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   static_assert(C_ % 4 == 0 && R_ <= 64 && C_ <= 32 && (R_ + 2 * kRing) * PC <= 2048, "lean kernel geometry");
   static_assert(NW == 1 || (NW == 2 && !STAMP && Q % 2 == 0), "two waves: the plain form, even Q");
   constexpr int QW = Q / NW;          // observation quads per lane this wave stores
-  constexpr int kStores = 3 * QW + 4;  // a wave's stores per tick (see 6. below)
+  static_assert(!REC || !STAMP, "record output: the plain instances only");
+  constexpr int NVIS = (RC + 31) / 32;       // record: visibility words,
+  constexpr int RW = (NVIS + 1 + 3) & ~3;    // words in all (position word, zero pad to 16 bytes)
+  // a wave's vector-memory operations per tick after the DMA (see 6. below): 3 per quad and
+  // reward, reward64, done, status; REC: one record-word store per quad, the position / pad
+  // store, and the same four
+  constexpr int kStores = REC ? QW + 1 + 4 : 3 * QW + 4;
   extern __shared__ __align__(16) unsigned char smem[];
   const int e = block_env(p);
   if (p.prio_mode && p.dispatch_order) {  // never taken (prio_mode is always 0): see EnvParams::dispatch_order
@@ -2474,7 +2556,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     ivl = base_ok && !fan_ok && p.interval_fans && __ballot(!ivl_cam) == 0ull;
     if (!base_ok || (!fan_ok && !ivl)) {
       if (NW == 2 && wid != 0) return;  // the generic body is one wave's (an ended wave leaves the barriers)
-      lean_generic_body<D>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
+      lean_generic_body<D, REC>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, smem, e);
       return;
     }
     if (live_cam) {
@@ -2923,37 +3005,57 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     LEAN_STAMP(6);  // 6: auto-reset
     // 6. tick k's stores (kStores, unconditional; lanes with nothing to store pass an offset
     // past their buffer descriptor, which the hardware drops): observation channels 0, 1, 2
-    // (Q quads per lane each), reward, reward64, done, status
+    // (Q quads per lane each) or, REC, the record's words, then reward, reward64, done, status
     asm volatile("" ::: "memory");
-    constexpr int pol = 2;  // nt (policy A/B: profiles/r02ba_probe_obs_store.log; sc1 nt 3 % slower here, r05w)
-    float* o = obs + ((size_t)k * N + e) * 3 * RC;
-    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o, (short)0, 12 * RC, 0x00020000);
-    const int sol = s.pos_r * C_ + s.pos_c, qs = sol >> 2;
-    const int vault = p.vr * C_ + p.vc;
+    if constexpr (REC) {
+      // the record (heist_obs.hip): quad q's nibble sits at bit 4 (q & 7) of word q >> 3, so 8
+      // consecutive lanes hold one word; lane 8 w of the group stores it.  A quad past N4 adds
+      // nothing (bits past R C stay 0) and a word past NVIS is not stored; then lanes 0 ..
+      // RW - NVIS - 1 of wave 0 store the position word (s after the auto-reset: a reset row
+      // holds the start cell) and the zero pad.  QW + 1 stores, every lane of every wave.
+      uint32_t* o = obs + ((size_t)k * N + e) * RW;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o, (short)0, 4 * RW, 0x00020000);
 #pragma unroll
-    for (int j = 0; j < QW; ++j) {
-      const int q = lane + 64 * (wid * QW + j);
-      const bool in = q < N4;
-      const int qc = in ? q : N4 - 1;
-      const uint32_t b = *reinterpret_cast<const uint32_t*>(L.grid + 4 * qc);
-      // float32(tile) / 5 == float32(tile) * 0.2f for every tile type (environment.py:319)
-      obs_put(rs, pol, in ? 16 * q : (int)kOOB,
-              make_float4((float)(b & 0xff) * 0.2f, (float)((b >> 8) & 0xff) * 0.2f,
-                          (float)((b >> 16) & 0xff) * 0.2f, (float)(b >> 24) * 0.2f));
-      const uint32_t v = v1[j];
-      obs_put(rs, pol, in ? 16 * (N4 + q) : (int)kOOB,
-              make_float4((float)(v & 0xff), (float)((v >> 8) & 0xff), (float)((v >> 16) & 0xff), (float)(v >> 24)));
-      float4 c2 = L.plane2[qc];
-      // the solver's cell of channel 2 is fl32(1 + g) for its static value g (heist_create's
-      // second plane), unless it is the vault, whose value wins: patched in the register of
-      // the lane that stores its quad (one store per quad, no second write of the line)
-      const bool pl = q == qs && sol != vault;
-      const int m = sol & 3;
-      c2.x = pl && m == 0 ? 1.0f + c2.x : c2.x;
-      c2.y = pl && m == 1 ? 1.0f + c2.y : c2.y;
-      c2.z = pl && m == 2 ? 1.0f + c2.z : c2.z;
-      c2.w = pl && m == 3 ? 1.0f + c2.w : c2.w;
-      obs_put(rs, pol, in ? 16 * (2 * N4 + q) : (int)kOOB, c2);
+      for (int j = 0; j < QW; ++j) {
+        const int q = lane + 64 * (wid * QW + j);
+        uint32_t w = (q < N4 ? vis_nibble(v1[j]) : 0u) << (4 * (lane & 7));
+        w = or8_lanes(w);
+        const int wi = q >> 3;
+        __builtin_amdgcn_raw_buffer_store_b32(w, rs, (lane & 7) == 0 && wi < NVIS ? 4 * wi : (int)kOOB, 0, 0);
+      }
+      __builtin_amdgcn_raw_buffer_store_b32(lane == 0 ? (uint32_t)s.pos_r | ((uint32_t)s.pos_c << 8) : 0u, rs,
+                                            wid == 0 && lane < RW - NVIS ? 4 * (NVIS + lane) : (int)kOOB, 0, 0);
+    } else {
+      constexpr int pol = 2;  // nt (policy A/B: profiles/r02ba_probe_obs_store.log; sc1 nt 3 % slower here, r05w)
+      float* o = obs + ((size_t)k * N + e) * 3 * RC;
+      const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(o, (short)0, 12 * RC, 0x00020000);
+      const int sol = s.pos_r * C_ + s.pos_c, qs = sol >> 2;
+      const int vault = p.vr * C_ + p.vc;
+  #pragma unroll
+      for (int j = 0; j < QW; ++j) {
+        const int q = lane + 64 * (wid * QW + j);
+        const bool in = q < N4;
+        const int qc = in ? q : N4 - 1;
+        const uint32_t b = *reinterpret_cast<const uint32_t*>(L.grid + 4 * qc);
+        // float32(tile) / 5 == float32(tile) * 0.2f for every tile type (environment.py:319)
+        obs_put(rs, pol, in ? 16 * q : (int)kOOB,
+                make_float4((float)(b & 0xff) * 0.2f, (float)((b >> 8) & 0xff) * 0.2f,
+                            (float)((b >> 16) & 0xff) * 0.2f, (float)(b >> 24) * 0.2f));
+        const uint32_t v = v1[j];
+        obs_put(rs, pol, in ? 16 * (N4 + q) : (int)kOOB,
+                make_float4((float)(v & 0xff), (float)((v >> 8) & 0xff), (float)((v >> 16) & 0xff), (float)(v >> 24)));
+        float4 c2 = L.plane2[qc];
+        // the solver's cell of channel 2 is fl32(1 + g) for its static value g (heist_create's
+        // second plane), unless it is the vault, whose value wins: patched in the register of
+        // the lane that stores its quad (one store per quad, no second write of the line)
+        const bool pl = q == qs && sol != vault;
+        const int m = sol & 3;
+        c2.x = pl && m == 0 ? 1.0f + c2.x : c2.x;
+        c2.y = pl && m == 1 ? 1.0f + c2.y : c2.y;
+        c2.z = pl && m == 2 ? 1.0f + c2.z : c2.z;
+        c2.w = pl && m == 3 ? 1.0f + c2.w : c2.w;
+        obs_put(rs, pol, in ? 16 * (2 * N4 + q) : (int)kOOB, c2);
+      }
     }
     const uint32_t ko = (uint32_t)((size_t)k * N + e);
     const int l0 = lane == 0 && wid == 0 ? 0 : (int)kOOB;
@@ -3635,63 +3737,93 @@ MultiRoute multi_route(const EnvParams& p) {
   return r;
 }
 
-hipError_t launch_step_multi(const EnvParams& p, int K, const int64_t* actions, float* obs,
-                             float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
-                             hipStream_t st) {
+// REC: the record-output instances (obs is the record array); only the plain lean and generic
+// K-tick kernels have one, so another route is an error here (heist_step_multi_records takes
+// its fallback before it gets this far).
+template <bool REC>
+static hipError_t launch_step_multi_t(const EnvParams& p, int K, const int64_t* actions, obs_out_t<REC>* obs,
+                                      float* rew, double* rew64, uint8_t* done_out, int8_t* status_out,
+                                      int auto_reset, hipStream_t st) {
   const MultiRoute r = multi_route(p);
-  if (r.kind == MultiRoute::kSingleTicks) {
-    const size_t n = (size_t)p.n_envs;
-    for (int k = 0; k < K; ++k) {
-      const hipError_t e = launch_step(p, actions + k * n, obs + k * n * 3 * p.RC, rew + k * n, rew64 ? rew64 + k * n : nullptr,
-                                       done_out + k * n, status_out + k * n, auto_reset, st);
-      if (e != hipSuccess) return e;
+  if constexpr (REC) {
+    if ((r.kind != MultiRoute::kLean && r.kind != MultiRoute::kGeneric) || r.stamped) return hipErrorInvalidValue;
+  } else {
+    if (r.kind == MultiRoute::kSingleTicks) {
+      const size_t n = (size_t)p.n_envs;
+      for (int k = 0; k < K; ++k) {
+        const hipError_t e = launch_step(p, actions + k * n, obs + k * n * 3 * p.RC, rew + k * n, rew64 ? rew64 + k * n : nullptr,
+                                         done_out + k * n, status_out + k * n, auto_reset, st);
+        if (e != hipSuccess) return e;
+      }
+      return hipSuccess;
     }
-    return hipSuccess;
   }
   const size_t lds = step_multi_lds(p, K);
-  if (r.kind == MultiRoute::kProbe) {
+  if constexpr (!REC) {
+    if (r.kind == MultiRoute::kProbe) {
 #define HEIST_PROBE_CASE(W_, M)                                                                              \
   if (p.multi_waves == W_ && p.probe_mode == M)                                                              \
     hipLaunchKernelGGL((step_multi_kernel<W_, 1024, false, M>), dim3(p.n_envs), dim3(64 * W_), lds, st, p, K, \
                        actions, obs, rew, rew64, done_out, status_out, auto_reset);
-    HEIST_PROBE_CASE(2, 1) HEIST_PROBE_CASE(2, 2) HEIST_PROBE_CASE(2, 3) HEIST_PROBE_CASE(2, 4)
-    HEIST_PROBE_CASE(1, 1) HEIST_PROBE_CASE(1, 2) HEIST_PROBE_CASE(1, 3) HEIST_PROBE_CASE(1, 4)
+      HEIST_PROBE_CASE(2, 1) HEIST_PROBE_CASE(2, 2) HEIST_PROBE_CASE(2, 3) HEIST_PROBE_CASE(2, 4)
+      HEIST_PROBE_CASE(1, 1) HEIST_PROBE_CASE(1, 2) HEIST_PROBE_CASE(1, 3) HEIST_PROBE_CASE(1, 4)
 #undef HEIST_PROBE_CASE
-    return hipGetLastError();
+      return hipGetLastError();
+    }
   }
   if (p.fan_on && p.fan_fill) hipLaunchKernelGGL(fan_kernel, dim3(kFanTicks), dim3(kFanRays), 0, st, p);
   if (r.kind == MultiRoute::kLean) {
     const size_t lds_l = lean_lds_bytes(p, K);
-    if (r.grid == 20 && r.stamped)
-      hipLaunchKernelGGL((step_lean_kernel<20, 20, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
-                         rew64, done_out, status_out, auto_reset);
-    else if (r.grid == 20)
-      hipLaunchKernelGGL((step_lean_kernel<20, 20>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew, rew64,
-                         done_out, status_out, auto_reset);
-    else if (r.stamped)
-      hipLaunchKernelGGL((step_lean_kernel<32, 32, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
-                         rew64, done_out, status_out, auto_reset);
+    if constexpr (!REC) {
+      if (r.stamped) {
+        if (r.grid == 20)
+          hipLaunchKernelGGL((step_lean_kernel<20, 20, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs,
+                             rew, rew64, done_out, status_out, auto_reset);
+        else
+          hipLaunchKernelGGL((step_lean_kernel<32, 32, true>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs,
+                             rew, rew64, done_out, status_out, auto_reset);
+        return hipGetLastError();
+      }
+    }
+    if (r.grid == 20)
+      hipLaunchKernelGGL((step_lean_kernel<20, 20, false, 1, REC>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions,
+                         obs, rew, rew64, done_out, status_out, auto_reset);
     else if (r.waves == 2)
-      hipLaunchKernelGGL((step_lean_kernel<32, 32, false, 2>), dim3(p.n_envs), dim3(128), lds_l, st, p, K, actions,
+      hipLaunchKernelGGL((step_lean_kernel<32, 32, false, 2, REC>), dim3(p.n_envs), dim3(128), lds_l, st, p, K, actions,
                          obs, rew, rew64, done_out, status_out, auto_reset);
     else
-      hipLaunchKernelGGL((step_lean_kernel<32, 32>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions, obs, rew,
-                         rew64, done_out, status_out, auto_reset);
+      hipLaunchKernelGGL((step_lean_kernel<32, 32, false, 1, REC>), dim3(p.n_envs), dim3(64), lds_l, st, p, K, actions,
+                         obs, rew, rew64, done_out, status_out, auto_reset);
     return hipGetLastError();
   }
 #define HEIST_MULTI_CASE(W, D)                                                                             \
   if (p.multi_waves == W && p.vis_gap == D) {                                                              \
-    if (r.stamped)                                                                                         \
-      hipLaunchKernelGGL((step_multi_kernel<W, D, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,     \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                      \
-    else                                                                                                   \
-      hipLaunchKernelGGL((step_multi_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,           \
-                         actions, obs, rew, rew64, done_out, status_out, auto_reset);                      \
+    if constexpr (!REC) {                                                                                  \
+      if (r.stamped) {                                                                                     \
+        hipLaunchKernelGGL((step_multi_kernel<W, D, true>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K,   \
+                           actions, obs, rew, rew64, done_out, status_out, auto_reset);                    \
+        return hipGetLastError();                                                                          \
+      }                                                                                                    \
+    }                                                                                                      \
+    hipLaunchKernelGGL((step_multi_kernel<W, D, false, 0, REC>), dim3(p.n_envs), dim3(64 * W), lds, st, p, K, \
+                       actions, obs, rew, rew64, done_out, status_out, auto_reset);                        \
     return hipGetLastError();                                                                              \
   }
   HEIST_MULTI_VARIANTS(HEIST_MULTI_CASE)
 #undef HEIST_MULTI_CASE
   return hipErrorInvalidValue;  // not reached: multi_route only names a variant that exists
+}
+
+hipError_t launch_step_multi(const EnvParams& p, int K, const int64_t* actions, float* obs,
+                             float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
+                             hipStream_t st) {
+  return launch_step_multi_t<false>(p, K, actions, obs, rew, rew64, done_out, status_out, auto_reset, st);
+}
+
+hipError_t launch_step_multi_records(const EnvParams& p, int K, const int64_t* actions, uint32_t* records,
+                                     float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
+                                     hipStream_t st) {
+  return launch_step_multi_t<true>(p, K, actions, records, rew, rew64, done_out, status_out, auto_reset, st);
 }
 
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

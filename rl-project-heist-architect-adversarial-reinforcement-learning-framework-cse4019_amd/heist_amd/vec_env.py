@@ -269,6 +269,53 @@ class HeistEnv:
                       "heist_step_multi")
         return obs_out, rew, done.view(torch.bool), status, r64
 
+    @property
+    def records_direct(self) -> int:
+        """heist_step_records_direct: 1 when step_multi_records' launch writes the records from
+        the K-tick kernel itself (no observation row is written), 0 when it steps tick by tick
+        into a scratch row and packs it (no K-tick kernel for the grid, or counters, stamps or a
+        probe mode armed)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_step_records_direct(self._h))
+        nat.check(0 if d >= 0 else d, "heist_step_records_direct")
+        return d
+
+    def step_multi_records(self, actions: torch.Tensor, records_out: Optional[torch.Tensor] = None,
+                           auto_reset: Optional[bool] = None, reward64: bool = False):
+        """step_multi with every tick's observation as its compact record (heist_step_multi_records):
+        records[k] equals pack_obs of step_multi's obs[k], and reward, done, status, reward64 and
+        the envs' state afterwards are step_multi's.  Returns (records [K,N,W] int32, reward [K,N]
+        f32, done [K,N] bool, status [K,N] int8, reward64 [K,N] f64 or None); the records feed
+        CompactObs.of_env(env, records).  env.obs is not updated."""
+        from .obs_compact import record_words
+        a = actions
+        if a.device != self.device or a.dtype != torch.int64 or not a.is_contiguous():
+            a = a.to(device=self.device, dtype=torch.int64).contiguous()
+        if a.dim() != 2 or a.shape[1] != self.n_envs:
+            raise ValueError("step_multi_records: actions must be [K, %d]" % self.n_envs)
+        K = int(a.shape[0])
+        kw = dict(device=self.device)
+        shape = (K, self.n_envs, record_words(self.rows, self.cols))
+        if records_out is None:
+            records_out = torch.empty(shape, dtype=torch.int32, **kw)
+        elif (tuple(records_out.shape) != shape or records_out.dtype != torch.int32 or records_out.device != self.device
+              or not records_out.is_contiguous() or records_out.data_ptr() % 16):
+            raise ValueError("step_multi_records: records_out must be a contiguous, 16-byte aligned int32 %s tensor on %s"
+                             % (shape, self.device))
+        rew = torch.empty((K, self.n_envs), dtype=torch.float32, **kw)
+        r64 = torch.empty((K, self.n_envs), dtype=torch.float64, **kw) if reward64 else None
+        done = torch.empty((K, self.n_envs), dtype=torch.uint8, **kw)
+        status = torch.empty((K, self.n_envs), dtype=torch.int8, **kw)
+        ar = self.auto_reset if auto_reset is None else auto_reset
+        # the fallback's one scratch row (stream-ordered: the allocator keeps it until the work is done)
+        scratch = None if self.records_direct else torch.empty_like(self.obs)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_step_multi_records(self._h, K, nat.ptr(a), nat.ptr(records_out), nat.ptr(rew),
+                                                         nat.ptr(r64), nat.ptr(done), nat.ptr(status), 1 if ar else 0,
+                                                         nat.ptr(scratch), self._stream()),
+                      "heist_step_multi_records")
+        return records_out, rew, done.view(torch.bool), status, r64
+
     def step_multi_raw(self, K: int, actions: torch.Tensor, obs_out: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, status: torch.Tensor, auto_reset: bool = True) -> None:
         """heist_step_multi on caller-owned buffers with no checks or allocation (the

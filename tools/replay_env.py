@@ -6,6 +6,11 @@ under the given actions, printing one line per tick: tick, action, reward (float
 
   python tools/replay_env.py state.pt --env 137 --actions 4,4,2,0,1
   python tools/replay_env.py checkpoints/env_ep250.pt --env 5 --actions-file acts.txt --auto-reset
+  python tools/replay_env.py state.pt --env 137 --actions-file long.txt --records
+
+--records replays through HeistEnv.step_multi_records (launches of up to 1024 ticks whose rows are
+64-byte records, not observations) and prints the same lines: the position is the record's
+position word, and nothing is expanded that is not printed.
 
 The reward constants are not part of a saved state: pass --rewards step,detection,vault when the
 run used others than EnvironmentConfig's defaults.
@@ -36,6 +41,8 @@ def main(argv=None):
     ap.add_argument("--actions-file", help="whitespace- or comma-separated actions")
     ap.add_argument("--auto-reset", action="store_true", help="reset the env when it finishes, as training does")
     ap.add_argument("--rewards", help="reward_step,reward_detection,reward_vault")
+    ap.add_argument("--records", action="store_true",
+                    help="replay in K-tick launches that emit compact records (same output)")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args(argv)
     st = load_states(args.state)
@@ -61,6 +68,21 @@ def main(argv=None):
     print("env %d of %s: pos (%d, %d) tick %d done %d, %d cameras, %d guards, %d walls" % (
         args.env, args.state, int(ex["pos_r"][0]), int(ex["pos_c"][0]), int(ex["tick"][0]), int(ex["done"][0]),
         int(ex["n_cams"][0]), int(ex["n_guards"][0]), int(ex["n_walls"][0])))
+    if args.records:
+        from heist_amd.obs_compact import record_words
+        nvis = (c["rows"] * c["cols"] + 31) // 32
+        assert nvis < record_words(c["rows"], c["cols"])
+        for k0 in range(0, len(acts), 1024):
+            chunk = acts[k0:k0 + 1024]
+            rec, _, done, status, r64 = env.step_multi_records(torch.tensor(chunk).reshape(-1, 1), reward64=True)
+            pos = rec[:, 0, nvis].cpu().tolist()  # pos_r | pos_c << 8
+            r64, done, status = r64[:, 0].cpu().tolist(), done[:, 0].cpu().tolist(), status[:, 0].cpu().tolist()
+            for j, a in enumerate(chunk):
+                print("%4d  action %d  reward %r  done %d  status %s  pos (%d, %d)" % (
+                    k0 + j, a, float(r64[j]), int(done[j]), STATUS_NAMES[int(status[j])], pos[j] & 0xff,
+                    (pos[j] >> 8) & 0xff))
+        env.close()
+        return
     for k, a in enumerate(acts):
         env.step(torch.tensor([a]))
         ex = env.export()
