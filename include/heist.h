@@ -215,6 +215,37 @@ int heist_step_multi_records(heist_t h, int K, const int64_t* actions, uint32_t*
                              double* reward64_out, uint8_t* done_out, int8_t* status_out, int auto_reset,
                              float* obs_scratch, heist_stream_t stream);
 
+/* Exact Solver planner, no reference counterpart: for every env in its current state, the fewest
+ * ticks in which some action sequence fed to heist_step_multi(..., auto_reset = 0) ends a tick with
+ * vault_reached == 1 and detected == 0, and one such sequence.  Cameras and guards move on a
+ * schedule the Solver does not influence (environment.py:250-258), so with
+ *   reach_0 = {the solver's cell} (empty for an env already done),
+ *   cand_k  = (reach_{k-1} and its four one-cell shifts inside the grid) minus wall cells,
+ *   vis_k   = the visibility plane heist_step would compute on the env's k-th tick from now,
+ * T is the first k >= 1 with vault in cand_k \ vis_k, and reach_k = cand_k \ vis_k \ {vault}, empty
+ * once tick + k >= max_steps (the arrival on the tick that times out still counts).  Env e plans
+ * min(horizon, max_steps - tick[e]) ticks.
+ *   ticks_out   [N] int32: T, or -1 when no k within those ticks qualifies (env done, no path,
+ *               the vault always seen on arrival, max_steps first, horizon too short).
+ *   actions_out [horizon][N] int64, heist_step_multi's `actions` as it stands: rows 0 .. T-1 hold
+ *               the canonical plan -- from x_T = vault, a_k is the lowest action (0 WAIT, 1 UP, 2
+ *               DOWN, 3 LEFT, 4 RIGHT) with x_k - delta(a_k) in reach_{k-1}, that cell being
+ *               x_{k-1} -- and every other entry is 0.
+ *   reach_out   [horizon][N][W] uint32, W = heist_obs_record_bytes(rows, cols) / 4, 16-byte aligned,
+ *               required (it is also the backtrack's history): row k-1 holds reach_k in the record's
+ *               bit order (bit i of word j is cell 32 j + i), words past ceil(R*C/32) are 0, rows of
+ *               ticks >= T and rows after the set empties are 0.
+ * The launch only reads the env: state, shared-fan bookkeeping, counters and stamps are untouched
+ * and a later launch gives, bit for bit, what it would have given without the call.
+ * heist_plan_supported: 1 when a planner kernel exists for the handle's (K-tick waves, grid size
+ *   class) -- every grid up to 64 x 64 at the default waves, cols need not be a multiple of 4 --
+ *   else 0; -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, a NULL ticks_out, actions_out or reach_out, reach_out not
+ * 16-byte aligned, a probe mode armed (HEIST_PROBE_MODE), heist_plan_supported 0. */
+int heist_plan_supported(heist_t h);
+int heist_plan(heist_t h, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
+               heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

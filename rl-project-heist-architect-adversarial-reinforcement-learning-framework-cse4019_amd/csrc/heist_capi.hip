@@ -31,6 +31,9 @@ hipError_t launch_step_multi_records(const EnvParams& p, int K, const int64_t* a
                                      hipStream_t st);
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,
                          double* guard_heading, hipStream_t st);
+bool plan_variant_exists(const EnvParams& p);
+hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
+                       hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
                       hipStream_t st);
 int vis_gap_for(int R, int C);
@@ -537,6 +540,31 @@ int heist_step_multi_records(heist_t h, int K, const int64_t* actions, uint32_t*
       return rc;
   }
   return 0;
+}
+
+int heist_plan_supported(heist_t h) {
+  if (check_handle(h)) return -1;
+  return heist::plan_variant_exists(h->p) ? 1 : 0;
+}
+
+int heist_plan(heist_t h, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
+               heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(ticks_out && actions_out && reach_out, "heist_plan: null output");
+  HEIST_REQUIRE(((uintptr_t)reach_out & 15) == 0, "heist_plan: reach_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)ticks_out & 3) == 0 && ((uintptr_t)actions_out & 7) == 0,
+                "heist_plan: ticks_out / actions_out misaligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan: a probe mode is armed (HEIST_PROBE_MODE)");
+  HEIST_REQUIRE(heist::plan_variant_exists(h->p), "heist_plan: no planner kernel for this handle "
+                                                  "(heist_plan_supported is 0)");
+  // the launch's own EnvParams: no shared fan (every camera cast live; fan_pos stays as it is)
+  EnvParams q = h->p;
+  q.fan_on = 0;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  return check_hip(heist::launch_plan(q, horizon, ticks_out, actions_out, reach_out, (hipStream_t)stream),
+                   "heist_plan");
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

@@ -2230,6 +2230,240 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(multi_oc
 }
 
 // ---------------------------------------------------------------------------
+// Exact Solver planner (heist_plan): fewest undetected ticks to the vault, per env
+// ---------------------------------------------------------------------------
+//
+// Cameras and guards move on a schedule the Solver does not influence (environment.py:250-258),
+// so the cells a live, unseen Solver can stand on after k ticks form a bit-set recurrence over
+// time whose only input is the tick's visibility plane:
+//   cand_k  = (reach_{k-1} | its four one-cell shifts inside the grid) minus walls
+//   T       = the first k with vault in cand_k \ vis_k
+//   reach_k = cand_k \ vis_k \ {vault}, empty once tick + k >= max_steps
+// One workgroup per env, W waves, the prologue and the tick's emitter update / publish / raycast /
+// cone stamps of step_multi_body with the Solver taken out: the emitters always advance (the
+// planned Solver is alive), every camera is cast live (no shared fan: the planner neither reads
+// nor advances the handle's fan table) and nothing is written back to the env.
+// The sets are ceil(R C / 64) pairs of 32-bit words in LDS, double-buffered (the record's bit order: cell i is
+// bit i & 31 of word i >> 5).  The DP step runs one cell per lane, 64 cells (two words) per wave
+// pass: the lane tests its own bit and its four neighbours' in the previous set (the row / column
+// tests are the cell's own, so a grid row that straddles a word needs no edge mask), its grid
+// byte and its byte of ray plane | guard plane, and one ballot packs the 64 results into the two
+// words of the next set -- the same ballot that would pack the visibility alone.  The words go
+// out to reach_out (row k - 1 = reach_k) after the barrier that completes them; the loop ends, block
+// uniformly, at the first clean vault arrival, when the set empties, or at the horizon, and the
+// rows left are zero-filled.  Then wave 0 walks back from the vault through the env's own rows
+// (lanes 0..4 test one action each, the lowest set lane of the ballot is the canonical action:
+// T dependent reads) and writes the env's column of actions_out and its ticks_out.
+// Waves per SIMD the planner is compiled for: 5 leaves 96 VGPRs, which every instance fits without
+// a spill (the K-tick kernel's 8 would hold the instances of two or more waves to 64 and spill 57).
+constexpr int plan_occ(int W) { return W == 1 ? 4 : 5; }
+
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_kernel(
+    EnvParams p, int H, int32_t* __restrict__ ticks_out, int64_t* __restrict__ actions_out, uint32_t* reach_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr bool SOLO = W == 1;
+  const int e = block_env(p);
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, N = p.n_envs, C = p.C;
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // cached guard cones of the tick, vis geometry
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6, NWP = 2 * n_chunk;  // 64-cell chunks; words per set, padded to a pair
+  uint32_t* sets = reinterpret_cast<uint32_t*>(uq + 128 * W);  // [2][NWP] reach sets, tick parity
+  int* flags = reinterpret_cast<int*>(sets + 2 * NWP);         // [2] per tick parity: 1 set not empty, 2 vault hit
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;       // the record's words (obs_record_words)
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;
+    prefetch<NT>(p, e, eb, L, raw);
+    if (t < n_slot) rec[t] = raw;
+  }
+  for (int i = t; i < path_words; i += NT) L.path[i] = eb.paths[i];
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  // ticks this env plans: the horizon, cut at max_steps (the arrival on the tick that times out
+  // still counts, the set after it is empty); none for an env already done
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  for (int i = t; i < 2 * NWP; i += NT) sets[i] = 0u;
+  if (t < 2) flags[t] = 0;
+  const int g = t - mc;
+  const bool live_cam = t < s.n_cams, live_guard = g >= 0 && g < s.n_guards;
+  bool cached = false;
+  uint4 ca = make_uint4(0u, 0u, 0u, 0u), cb = ca;
+  // a cached guard's cone entry for the coming tick, loaded one tick ahead (step_multi_body)
+  auto next_entry = [&](const Guard& gd) {
+    int idx = gd.idx, slot = gd.hslot;
+    if (gd.len >= 2) {
+      idx += gd.step;
+      if (idx >= gd.len) idx -= gd.len;
+      slot = gd.nslot;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(eb.cones + cone_off(g, idx, slot));
+    ca = src[0];
+    cb = src[1];
+  };
+  auto take_entry = [&]() {
+    Guard gd = as_guard(rec[t]);
+    gd.nslot = (uint8_t)(cb.w >> 16);  // row 15
+    rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+    uint4* dst = reinterpret_cast<uint4*>(L.cone + 16 * g);
+    dst[0] = ca;
+    dst[1] = cb;
+  };
+  __syncthreads();  // records in LDS, sets cleared
+  if (HK > 0) {
+    if (live_guard) {
+      const Guard gd = as_guard(rec[t]);
+      cached = gd.hslot != kUncached;
+      if (cached) next_entry(gd);
+    }
+    if (t == 0) {  // reach_0: the solver's cell
+      const int c0 = s.pos_r * C + s.pos_c;
+      sets[c0 >> 5] = 1u << (c0 & 31);
+    }
+  }
+  // cell / C as a multiply-shift: exact for cell < 2^20 / (m C - 2^20) >= 2^20 / 64 > R C
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+  const int vcell = p.vr * C + p.vc;
+
+  int T = -1, stored = 0;  // rows of reach_out this env has written
+  for (int k = 1; k <= HK; ++k) {
+    // (the barrier that closed the previous tick's DP step also closed its readers of vis / em / cones)
+    Emit E;
+    E.kind = -1;
+    if (w0) {
+      // cameras rotate, guards patrol (security.py:49-51, :145-159), unconditionally
+      if (live_cam) {
+        Cam cm = as_cam(rec[t]);
+        cm.heading = py_mod360(cm.heading + cm.speed * 1.0);
+        rec[t] = __builtin_bit_cast(EmitterRaw, cm);
+        E = cam_emit(cm);
+      } else if (live_guard) {
+        Guard gd = as_guard(rec[t]);
+        const bool moves = gd.len >= 2;
+        int nidx = gd.idx;
+        if (moves) {
+          nidx += gd.step;
+          if (nidx >= gd.len) nidx -= gd.len;
+        }
+        const uint16_t np = moves ? L.path[__umul24((uint32_t)g, (uint32_t)p.max_path) + (uint32_t)nidx] : gd.pos;
+        if (cached) {
+          if (moves) gd.hslot = gd.nslot;
+        } else if (moves) {
+          gd.heading = guard_heading_after(p, unpack_r(np) - unpack_r(gd.pos), unpack_c(np) - unpack_c(gd.pos),
+                                           gd.heading);
+        }
+        gd.idx = (int16_t)nidx;
+        gd.pos = np;
+        rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+        E = guard_emit(gd);
+        if (cached && !SOLO) take_entry();
+      }
+      publish_emitters(L, E, n_slot);
+    }
+    clear_planes<NT>(p, L, gvis, true);
+    __syncthreads();  // emitter table, cone rows, cleared planes
+    if (t == 0) flags[(k + 1) & 1] = 0;  // the next tick's; its last readers (tick k - 1's exit test) are past the barrier
+    if (live_guard && E.kind == 1) L.vis[L.at(E.row, E.col)] = 1;  // visibility.py:59
+    cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+    if (SOLO && cached) take_entry();
+    stamp_guard_cones<NT>(L, gvis, mc, mg, 0);
+    __syncthreads();  // planes complete
+
+    // the DP step: set k & 1 from set (k - 1) & 1, one cell per lane
+    const uint32_t* cur = sets + ((k - 1) & 1) * NWP;
+    uint32_t* nxt = sets + (k & 1) * NWP;
+    const bool last = tick0 + k >= p.max_steps;  // the env times out on this tick: no cell stays live
+    for (int ch = wave; ch < n_chunk; ch += W) {
+      const int cell = 64 * ch + lane;
+      bool on = false;
+      if (cell < RC) {
+        const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+        auto bit = [&](int i) { return (cur[i >> 5] >> (i & 31)) & 1u; };
+        uint32_t b = bit(cell);
+        if (c > 0) b |= bit(cell - 1);
+        if (c + 1 < C) b |= bit(cell + 1);
+        if (r > 0) b |= bit(cell - C);
+        if (r + 1 < p.R) b |= bit(cell + C);
+        const int a = L.at(r, c);
+        on = b != 0u && L.grid[cell] != kWall && (L.vis[a] | gvis[a]) == 0;
+      }
+      const unsigned long long hit = __ballot(on && cell == vcell);
+      const unsigned long long m = last ? 0ull : __ballot(on && cell != vcell);
+      if (lane == 0) {
+        *reinterpret_cast<uint2*>(nxt + 2 * ch) = make_uint2((uint32_t)m, (uint32_t)(m >> 32));
+        const int f = (m ? 1 : 0) | (hit ? 2 : 0);
+        if (f) atomicOr(&flags[k & 1], f);
+      }
+    }
+    if (w0 && live_guard && cached && k < HK) next_entry(as_guard(rec[t]));  // lands during the next tick
+    __syncthreads();  // the set and its flags complete
+    const int f = uni(flags[k & 1]);
+    if (f & 2) {  // block-uniform exits: the barriers stay safe
+      T = k;
+      break;
+    }
+    if (!(f & 1)) break;
+    uint32_t* row = reach_out + ((size_t)(k - 1) * N + e) * WR;
+    if (t < WR) row[t] = t < nvis ? nxt[t] : 0u;
+    for (int i = t + NT; i < WR; i += NT) row[i] = i < nvis ? nxt[i] : 0u;
+    stored = k;
+  }
+
+  // the rows this env did not write, 16 bytes per store (WR is a multiple of 4, reach_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - stored) * q4; i += NT) {
+      const int r = stored + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(reach_out + ((size_t)r * N + e) * WR)[q] = z;
+    }
+  }
+  for (int k = (T > 0 ? T : 0) + t; k < H; k += NT) actions_out[(size_t)k * N + e] = 0;
+  if (t == 0) ticks_out[e] = T;
+  if (T <= 0) return;  // block-uniform
+  __threadfence();     // this env's rows visible to the wave that reads them back
+  __syncthreads();
+  if (!w0) return;
+  // canonical backtrack: x_T = vault; a_k = the lowest action a with x_k - delta(a) in reach_{k-1}
+  int r = p.vr, c = p.vc;
+  const int dr = lane == 1 ? -1 : (lane == 2 ? 1 : 0), dc = lane == 3 ? -1 : (lane == 4 ? 1 : 0);
+  for (int k = T; k >= 1; --k) {
+    const int pr = r - dr, pc = c - dc;
+    bool ok = lane < 5 && pr >= 0 && pr < p.R && pc >= 0 && pc < C;
+    if (ok) {
+      const int cell = pr * C + pc;
+      if (k == 1) {
+        ok = pr == s.pos_r && pc == s.pos_c;
+      } else {
+        const uint32_t w = __hip_atomic_load(reach_out + ((size_t)(k - 2) * N + e) * WR + (cell >> 5), __ATOMIC_RELAXED,
+                                             __HIP_MEMORY_SCOPE_AGENT);
+        ok = (w >> (cell & 31)) & 1u;
+      }
+    }
+    const unsigned long long m = __ballot(ok);
+    const int a = m ? (int)__builtin_ctzll(m) : 0;  // m != 0: x_k came from a cell of reach_{k-1}
+    if (lane == 0) actions_out[(size_t)(k - 1) * N + e] = a;
+    r -= a == 1 ? -1 : (a == 2 ? 1 : 0);
+    c -= a == 3 ? -1 : (a == 4 ? 1 : 0);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean K-tick kernel (heist_step_multi, one wave per env, grids up to 20 x 20)
 // ---------------------------------------------------------------------------
 //
@@ -3824,6 +4058,36 @@ hipError_t launch_step_multi_records(const EnvParams& p, int K, const int64_t* a
                                      float* rew, double* rew64, uint8_t* done_out, int8_t* status_out, int auto_reset,
                                      hipStream_t st) {
   return launch_step_multi_t<true>(p, K, actions, records, rew, rew64, done_out, status_out, auto_reset, st);
+}
+
+// heist_plan: an instance of plan_kernel for every generic K-tick (waves, vis_gap); no condition
+// on the grid's columns (the planner stores no float4 observation quads).
+bool plan_variant_exists(const EnvParams& p) {
+  return multi_variant_exists(p.multi_waves, p.vis_gap) && p.max_cams + p.max_guards <= kMaxEmitters;
+}
+
+// The K-tick kernel's LDS without its action bytes and stamp sums, plus the two reach sets
+// (ceil(R C / 64) word pairs each) and the two exit flags.
+static size_t plan_lds(const EnvParams& p) {
+  const int n_slot = p.max_cams + p.max_guards;
+  return align16(env_lds_bytes(p.R, p.C, n_slot, p.max_guards * p.max_path, p.vis_gap, p.multi_waves, p.max_guards)) +
+         32 * (size_t)n_slot + (size_t)p.vis_gap + align16(sizeof(TieBuckets)) + 1024 * (size_t)p.multi_waves +
+         16 * (size_t)((p.RC + 63) >> 6) + 16;
+}
+
+hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
+                       hipStream_t st) {
+  if (!plan_variant_exists(p)) return hipErrorInvalidValue;
+  const size_t lds = plan_lds(p);
+#define HEIST_PLAN_CASE(W, D)                                                                                   \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                   \
+    hipLaunchKernelGGL((plan_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, horizon, ticks_out,       \
+                       actions_out, reach_out);                                                                 \
+    return hipGetLastError();                                                                                   \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_PLAN_CASE)
+#undef HEIST_PLAN_CASE
+  return hipErrorInvalidValue;  // not reached
 }
 
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

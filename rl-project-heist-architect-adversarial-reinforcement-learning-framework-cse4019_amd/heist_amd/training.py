@@ -158,7 +158,8 @@ class AdversarialTrainer:  # training.py:115-790
                  rollout_len: Optional[int] = None, minibatch: int = 4096, device=None, max_budget: Optional[int] = None,
                  seed: Optional[int] = None, update_precision: str = "fp32", rollout_precision: str = "fp32",
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
-                 solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False):
+                 solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
+                 track_optimal: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -197,6 +198,12 @@ class AdversarialTrainer:  # training.py:115-790
         # file continues the layouts where they stood instead of drawing new ones
         self.checkpoint_env = bool(checkpoint_env)
         self._env_restored = False
+        # True: every layout batch is planned once (HeistEnv.plan, right after its set_layout +
+        # reset) and train_iteration reports the latest batch's solvable_frac (layouts the Solver
+        # can finish undetected within max_steps) and optimal_ticks_mean (their fewest ticks);
+        # False: no launch, no metric, logs and checkpoints byte-identical
+        self.track_optimal = bool(track_optimal)
+        self._optimal = None  # (solvable_frac, optimal_ticks_mean) of the latest planned layout batch
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -328,9 +335,18 @@ class AdversarialTrainer:  # training.py:115-790
                 self.c[:, mb] = 0.0
                 self.b_valid[mb] = True
                 self.b_scored[mb] = False
+                if self.track_optimal:
+                    self._plan_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
+
+    def _plan_layout_batch(self, env_ids):
+        """The optimal tick counts of the layouts just set on env_ids (fresh after reset)."""
+        t = self.env.plan().ticks[torch.as_tensor(env_ids, device=self.device)]
+        ok = t > 0
+        n_ok, total = (int(x) for x in torch.stack([ok.sum(), (t * ok).sum()]).cpu())
+        self._optimal = (n_ok / len(env_ids), total / n_ok if n_ok else float("nan"))
 
     # -- rollout / scoring ------------------------------------------------------------------
     @torch.no_grad()
@@ -666,6 +682,8 @@ class AdversarialTrainer:  # training.py:115-790
         if reassign:
             self._assign_layouts(done_ids, ov, empty=self.warmup)
         out["layouts_scored"] = len(done_ids)
+        if self.track_optimal and self._optimal is not None:
+            out["solvable_frac"], out["optimal_ticks_mean"] = self._optimal
         return out
 
     # -- public API (training.py:336-416, :606-663) -------------------------------------------

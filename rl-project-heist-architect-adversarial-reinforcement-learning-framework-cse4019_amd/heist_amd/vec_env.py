@@ -96,6 +96,30 @@ def _layout_to_lists(lb: "LayoutBatch"):
 LayoutBatch.to_lists = _layout_to_lists
 
 
+@dataclass
+class PlanResult:
+    """HeistEnv.plan's output (heist_plan, include/heist.h), device tensors:
+    ticks [N] int32 -- the fewest ticks to a clean vault arrival, -1 when there is none in reach;
+    actions [H, N] int64 -- the canonical plan in rows 0 .. ticks - 1, 0 elsewhere: feed it (or
+        its first rows) to step_multi / step_multi_records with auto_reset=False;
+    reach [H, N, W] int32 -- row k - 1: the cells the Solver can occupy, live and unseen, after k
+        ticks, in the compact record's bit order (bit i of word j is cell 32 j + i)."""
+    ticks: torch.Tensor
+    actions: torch.Tensor
+    reach: torch.Tensor
+    rows: int
+    cols: int
+
+    def reach_mask(self, k: int) -> torch.Tensor:
+        """reach_k for k = 1 .. H as bool [N, R, C]."""
+        if not 1 <= k <= self.reach.shape[0]:
+            raise IndexError("reach_mask: k must be 1 .. %d" % self.reach.shape[0])
+        w = self.reach[k - 1]
+        sh = torch.arange(32, device=w.device, dtype=torch.int32)
+        bits = (w.unsqueeze(-1) >> sh) & 1
+        return bits.reshape(w.shape[0], -1)[:, :self.rows * self.cols].reshape(-1, self.rows, self.cols).bool()
+
+
 class HeistEnv:
     """Batched HeistEnvironment on one HIP device.
 
@@ -315,6 +339,32 @@ class HeistEnv:
                                                          nat.ptr(scratch), self._stream()),
                       "heist_step_multi_records")
         return records_out, rew, done.view(torch.bool), status, r64
+
+    # -- exact planner (heist_plan) ---------------------------------------------------------
+    @property
+    def plan_supported(self) -> int:
+        """heist_plan_supported: 1 when plan() has a kernel for this handle."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_supported")
+        return d
+
+    def plan(self, horizon: Optional[int] = None) -> "PlanResult":
+        """heist_plan: for every env as it stands, the fewest ticks in which the Solver can reach
+        the vault undetected, the canonical action sequence that does it (rows of a step_multi
+        `actions` tensor) and the set of cells it can occupy, live and unseen, after every tick.
+        horizon: ticks to look ahead (default config.max_steps, at most 1024); an env plans
+        min(horizon, max_steps - tick).  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        kw = dict(device=self.device)
+        ticks = torch.empty(self.n_envs, dtype=torch.int32, **kw)
+        actions = torch.empty((max(H, 0), self.n_envs), dtype=torch.int64, **kw)
+        reach = torch.empty((max(H, 0), self.n_envs, record_words(self.rows, self.cols)), dtype=torch.int32, **kw)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan(self._h, H, nat.ptr(ticks), nat.ptr(actions), nat.ptr(reach), self._stream()),
+                      "heist_plan")
+        return PlanResult(ticks, actions, reach, self.rows, self.cols)
 
     def step_multi_raw(self, K: int, actions: torch.Tensor, obs_out: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, status: torch.Tensor, auto_reset: bool = True) -> None:

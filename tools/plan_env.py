@@ -1,0 +1,120 @@
+"""The exact planner (heist_plan, HeistEnv.plan) on a batch of layouts: what share of them the
+Solver can finish undetected, in how many ticks at best, how many pass the BFS check and are
+unsolvable all the same -- and what the launch costs next to heist_step_multi_records, the
+existing launch that casts the same rays, same process, same handle, HIP events.
+
+  python tools/plan_env.py                       # bench.py's C2: 4,096 envs of 20 x 20, Architect layouts, horizon 200
+  python tools/plan_env.py --layouts synthetic   # random layouts instead of the checkpoint's
+  python tools/plan_env.py --layouts empty       # no walls, cameras or guards: every env plans exactly its
+                                                 # Manhattan distance in ticks, none casts a ray -- the cost
+                                                 # of the prologue, the DP step and the row stores alone
+  python tools/plan_env.py --ckpt checkpoints/architect_ep500.pt
+
+The planner only reads the envs, so every timed launch does the same work from the same state
+(fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
+the median is reported.  The records launches (K = horizon ticks of random actions, auto-reset)
+follow on the same handle, timed the same way.  Prints one JSON line.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "rl-project-heist-architect-adversarial-reinforcement-learning-framework-cse4019_amd"))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+import bench  # noqa: E402
+from heist_amd import EnvironmentConfig, HeistEnv  # noqa: E402
+from heist_amd.layouts import valid_synthetic_layouts  # noqa: E402
+
+
+def timed(dev, fn, warmup, runs):
+    """Milliseconds of each of `runs` calls of fn (one launch each), after `warmup` untimed ones."""
+    stream = torch.cuda.current_stream(dev)
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize(dev)
+    ms = []
+    for _ in range(runs):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record(stream)
+        fn()
+        b.record(stream)
+        torch.cuda.synchronize(dev)
+        ms.append(a.elapsed_time(b))
+    return ms
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--grid", type=int, default=20)
+    ap.add_argument("--budget", type=int, default=15)
+    ap.add_argument("--max-steps", type=int, default=200)
+    ap.add_argument("--horizon", type=int, default=None, help="default: max_steps (at most 1024)")
+    ap.add_argument("--layouts", choices=("architect", "synthetic", "empty"), default="architect")
+    ap.add_argument("--ckpt", default=None, help="Architect checkpoint (default: the fixed C2 one)")
+    ap.add_argument("--seed", type=int, default=1234)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--runs", type=int, default=7)
+    args = ap.parse_args(argv)
+    dev = torch.device("cuda:0")
+    torch.cuda.set_device(dev)
+    R, N, budget = args.grid, args.envs, args.budget
+    cfg = EnvironmentConfig(grid_rows=R, grid_cols=R, max_steps=args.max_steps, architect_budget=budget)
+    env = HeistEnv(N, cfg, max_cams=max(1, budget // 3), max_guards=max(1, budget // 5), max_path=16, device=dev,
+                   auto_reset=True)
+    if args.layouts == "architect":
+        bench.architect_layouts(env, budget, seed=args.seed, ckpt=args.ckpt)
+    elif args.layouts == "synthetic":
+        valid_synthetic_layouts(env, budget, seed=args.seed)
+    else:
+        env.set_layouts([([], [], [])] * N, budget=budget)
+    valid = env.valid.clone().bool()
+    env.reset()
+    H = min(args.horizon or args.max_steps, 1024)
+    kc = env.kernel_config()
+    assert env.plan_supported == 1, kc
+
+    res = env.plan(H)
+    ticks = res.ticks.cpu()
+    ok = ticks > 0
+    rows_live = (res.reach != 0).any(2).sum(0).cpu()  # reach rows that hold a cell
+    planned = torch.where(ok, ticks.long(), torch.clamp(rows_live + 1, max=H))  # ticks each env's block ran
+    hist = {}
+    for t in ticks[ok].tolist():
+        lo = t // 10 * 10
+        hist["%d-%d" % (lo, lo + 9)] = hist.get("%d-%d" % (lo, lo + 9), 0) + 1
+    plan_ms = timed(dev, lambda: env.plan(H), args.warmup, args.runs)
+
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(4321)
+    actions = torch.randint(0, 5, (H, N), device=dev, generator=gen, dtype=torch.int64)
+    rec_ms = timed(dev, lambda: env.step_multi_records(actions), args.warmup, args.runs)
+
+    p, r = statistics.median(plan_ms), statistics.median(rec_ms)
+    out = {"config": "%dx%d" % (R, R), "envs": N, "layouts": args.layouts, "horizon": H, "budget": budget,
+           "multi_waves": kc["multi_waves"], "records_kernel": bench.multi_kernel_name(kc, R, R),
+           "records_direct": env.records_direct,
+           "solvable_frac": float(ok.float().mean()), "bfs_valid": int(valid.sum()),
+           "bfs_valid_but_unsolvable": int((valid.cpu() & ~ok).sum()),
+           "optimal_ticks": {"min": int(ticks[ok].min()) if ok.any() else None,
+                             "mean": float(ticks[ok].float().mean()) if ok.any() else None,
+                             "max": int(ticks[ok].max()) if ok.any() else None, "histogram": hist},
+           "planned_ticks_mean": float(planned.float().mean()),
+           "plan": {"launch_ms_median": p, "launch_ms": plan_ms, "us_per_tick_of_horizon": p / H * 1e3,
+                    "us_per_planned_tick": p / float(planned.float().mean()) * 1e3,
+                    "ns_per_env_tick_planned": p * 1e6 / float(planned.sum())},
+           "records": {"launch_ms_median": r, "launch_ms": rec_ms, "us_per_tick": r / H * 1e3,
+                       "ns_per_env_tick": r * 1e6 / (H * N)}}
+    out["plan_over_records_per_tick_run"] = out["plan"]["us_per_planned_tick"] / out["records"]["us_per_tick"]
+    env.close()
+    print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
