@@ -160,6 +160,34 @@ int heist_state_save(heist_t h, const int32_t* env_ids, int m, void* blobs, heis
 int heist_state_load(heist_t h, const int32_t* env_ids, int m, const void* blobs, int n_blobs,
                      const int32_t* blob_index, uint8_t* status_out, heist_stream_t stream);
 
+/* Fork inside a handle, no reference counterpart: item i makes env dst_ids[i] equal to env
+ * src_ids[i] of the same handle (both int32 [m], device, required; a source may be named many
+ * times: one root, many children).  One launch, no blob, no rebuild, no scratch.
+ * After the call every later heist_step, heist_step_multi, heist_step_multi_records, heist_reset,
+ * heist_export, heist_plan, heist_state_save and heist_set_layout on dst gives, bit for bit, what
+ * the same call gives on src from this moment: heist_state_load's contract without the blob.
+ * An accepted item copies what a blob holds for the env -- scalars, every camera and guard record
+ * as it stands, paths, grid, stop map -- and the guard cone cache: for each live guard the source
+ * has cached, its cone block (the rows of its patrol points: every entry a later call can read)
+ * is copied from src, or kept where dst already held it.  It is kept
+ * exactly when, before the call, dst's guard of that index was live and cached and dst's grid,
+ * the guard's fov, step, length, range, rays and patrol start and its patrol points equalled
+ * src's (the block is a function of those: the usual case when the children of one root are
+ * forked again every few ticks).
+ *   status_out [m] uint8 (may be NULL):
+ *     0 rejected, dst untouched: an id outside [0, n_envs), src == dst, a dst that another item
+ *       names as dst (every such item is rejected) or that any item names as src
+ *     1 forked; every cached guard's cones copied, or the source has no cached guard
+ *     2 forked; every cached guard's cones kept
+ *     3 forked; some cones kept and some copied
+ * So sources are only read during the launch and every destination has one writer.  Like
+ * heist_state_load it recomputes the dispatch order and marks the K-tick fan table stale.  Two
+ * forks, or a fork and a load, on one handle must not run concurrently on different streams (a
+ * fork reads envs the other may be writing, and both rewrite the dispatch order).
+ * HEIST_EINVAL: m < 0, a NULL src_ids or dst_ids with m > 0.  m == 0 is a no-op. */
+int heist_state_fork(heist_t h, const int32_t* src_ids, const int32_t* dst_ids, int m, uint8_t* status_out,
+                     heist_stream_t stream);
+
 /* Compact observation records, no reference counterpart as an entry point: a lossless restatement
  * of get_state_tensor's output (environment.py:305-374) for callers that keep many observations
  * (the trainer's rollout buffer).  Channel 0 is grid / 5 and constant while a layout stands, channel

@@ -101,6 +101,8 @@ hipError_t launch_state_load(const EnvParams& p, const int32_t* env_ids, int m, 
                              hipStream_t st);
 hipError_t launch_state_guards(const EnvParams& p, const void* blobs, const uint8_t* loaded, const int32_t* src,
                                hipStream_t st);
+hipError_t launch_state_fork(const EnvParams& p, const int32_t* src_ids, const int32_t* dst_ids, int m,
+                             uint8_t* status_out, hipStream_t st);
 int obs_record_words(int R, int C);
 hipError_t launch_obs_pack(const float* obs, int64_t n, int R, int C, int vr, int vc, uint32_t* rec, hipStream_t st);
 hipError_t launch_obs_expand(const uint32_t* rec, int64_t n_rec, const int32_t* rec_env, const int64_t* index, int64_t m,
@@ -611,6 +613,19 @@ int heist_state_load(heist_t h, const int32_t* env_ids, int m, const void* blobs
                           "heist_state_load: guards"))
     return rc;
   return check_hip(heist::launch_order(h->p, st), "heist_state_load: order");
+}
+
+int heist_state_fork(heist_t h, const int32_t* src_ids, const int32_t* dst_ids, int m, uint8_t* status_out,
+                     heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(m >= 0, "heist_state_fork: m < 0");
+  if (m == 0) return 0;
+  HEIST_REQUIRE(src_ids != nullptr && dst_ids != nullptr, "heist_state_fork: src_ids or dst_ids is null");
+  hipStream_t st = (hipStream_t)stream;
+  h->fan_pos = -1;  // other cameras: the shared fan table is refilled by the next K-tick launch
+  if (int rc = check_hip(heist::launch_state_fork(h->p, src_ids, dst_ids, m, status_out, st), "heist_state_fork"))
+    return rc;
+  return check_hip(heist::launch_order(h->p, st), "heist_state_fork: order");
 }
 
 int heist_count_samples(heist_t h, uint64_t* counter) {

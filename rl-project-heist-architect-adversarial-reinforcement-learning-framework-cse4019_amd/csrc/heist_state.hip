@@ -1,4 +1,5 @@
-// heist_state.hip -- env state blobs: heist_state_save / heist_state_load (include/heist.h).
+// heist_state.hip -- env state blobs: heist_state_save / heist_state_load, and the blob-free
+// fork inside a handle: heist_state_fork (include/heist.h).
 //
 // A blob restates one env as the kernels keep it in HBM between launches (heist_device.h), so an
 // env loaded from it continues bit for bit.  Layout (StateLayout, every section 16-byte aligned):
@@ -15,6 +16,14 @@
 // patrol point 0, heading 0, no slots.  So a load is three launches: state_load_kernel writes
 // everything and the guards in that form, guard_cone_kernel fills the cones of the loaded envs,
 // state_guards_kernel puts the guards' saved pose back.  Loads and stores are plain vector ones.
+//
+// heist_state_fork (state_fork_kernel) copies env to env inside one handle without a blob: the
+// same records, and the cone blocks themselves instead of a rebuild.  It relies on, and keeps,
+// this invariant: the cone block of a live guard with hslot != kUncached is always
+// guard_cone_kernel's output for the env's current grid, that guard's static fields (fov, step,
+// len, range, num_rays, pos0) and its path.  heist_set_layout and heist_state_load rebuild the
+// block whenever those change; a fork either copies the block along with them or, where the
+// destination already holds equal ones under a cached guard, leaves the equal block in place.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -198,6 +207,122 @@ __global__ __launch_bounds__(256) void state_guards_kernel(EnvParams p, const ui
     gd.nslot = kUncached;
   }
   p.guards[(size_t)e * p.max_guards + g] = gd;
+}
+
+// lane's share of "n bytes at a and b differ" (any alignment; 16-byte words where both pointers
+// and n allow -- a wave-uniform choice)
+__device__ __forceinline__ bool bytes_differ(const uint8_t* a, const uint8_t* b, int n, int lane) {
+  bool diff = false;
+  if ((((uintptr_t)a | (uintptr_t)b | (uintptr_t)n) & 15) == 0) {
+    const uint4* x = reinterpret_cast<const uint4*>(a);
+    const uint4* y = reinterpret_cast<const uint4*>(b);
+    for (int i = lane; i < n / 16; i += 64) {
+      const uint4 u = x[i], v = y[i];
+      diff |= u.x != v.x || u.y != v.y || u.z != v.z || u.w != v.w;
+    }
+  } else {
+    for (int i = lane; i < n; i += 64) diff |= a[i] != b[i];
+  }
+  return diff;
+}
+
+// copy16 for the cone blocks: four loads in flight per lane before the first store
+__device__ __forceinline__ void copy16x4(uint16_t* dst, const uint16_t* src, int n16, int lane) {
+  uint4* d = reinterpret_cast<uint4*>(dst);
+  const uint4* s = reinterpret_cast<const uint4*>(src);
+  for (int i = lane; i < n16; i += 256) {
+    uint4 v[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (i + 64 * k < n16) v[k] = s[i + 64 * k];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (i + 64 * k < n16) d[i + 64 * k] = v[k];
+  }
+}
+
+// One wave per item: env dst_ids[i] <- env src_ids[i] of the same handle, no blob in between.
+// An item is rejected -- status 0, nothing written -- when an id is outside [0, n_envs), when
+// src == dst, when another item names its dst as dst (every such item is rejected) or when any
+// item names its dst as src: sources are only read during the launch and every destination has
+// one writer.  No address is formed from an id before that check.
+// An accepted item copies what a blob holds (scalars, cameras, guards as they stand, paths, grid,
+// stop map) and, per live guard g the source has cached (g < n_guards, hslot != kUncached), the
+// patrol-index rows [0, len) of its cone block -- every entry a tick, reset or plan can read (idx
+// < len) -- unless dst's block is kept.
+// The invariant the keep rule rests on: a live cached guard's cone block is guard_cone_kernel's
+// output for the env's current grid, that guard's static fields and its path (heist_set_layout
+// and heist_state_load rebuild it whenever those change; a fork copies it with them).  So the
+// block is kept exactly when, before the item wrote anything, dst's guard g was live and cached
+// and dst's grid bytes, the guard's fov, step, len, range, num_rays and pos0 and its first len
+// path points equalled src's.  (A record past dst's n_guards is a leftover of an earlier layout
+// whose cones another grid may have shaped: never kept.)  The comparisons read dst first; the
+// stores follow the ballots.
+// status: 1 every cached guard's cones copied (or none cached), 2 every one kept, 3 some of each.
+__global__ __launch_bounds__(64) void state_fork_kernel(EnvParams p, const int32_t* __restrict__ src_ids,
+                                                         const int32_t* __restrict__ dst_ids, int m,
+                                                         uint8_t* __restrict__ status_out) {
+  const int i = blockIdx.x, lane = threadIdx.x;
+  const int s = src_ids[i], d = dst_ids[i];
+  bool ok = (unsigned)s < (unsigned)p.n_envs && (unsigned)d < (unsigned)p.n_envs && s != d;
+  if (ok) {
+    bool clash = false;
+    for (int j = lane; j < m; j += 64) clash |= (j != i && dst_ids[j] == d) || src_ids[j] == d;
+    ok = !__any(clash);
+  }
+  if (!ok) {
+    if (status_out && lane == 0) status_out[i] = 0;
+    return;
+  }
+  const int mg = p.max_guards, mp = p.max_path;  // mg <= kMaxEmitters = 64: one lane per guard
+  const Guard* sg = p.guards + (size_t)s * mg;
+  Guard* dg = p.guards + (size_t)d * mg;
+  const uint16_t* sp = p.paths + (size_t)s * mg * mp;
+  uint16_t* dp = p.paths + (size_t)d * mg * mp;
+  const uint8_t* sgrid = p.grid + (size_t)s * p.RC;
+  uint8_t* dgrid = p.grid + (size_t)d * p.RC;
+  const int sng = min(p.scal[s].n_guards, mg), dng = min(p.scal[d].n_guards, mg);
+  bool cached = false, keep = false;
+  if (lane < sng) {
+    const Guard a = sg[lane];
+    cached = a.hslot != kUncached;
+    if (cached && lane < dng) {
+      const Guard b = dg[lane];
+      keep = b.hslot != kUncached && __builtin_bit_cast(uint64_t, a.fov) == __builtin_bit_cast(uint64_t, b.fov) &&
+             a.step == b.step && a.len == b.len && a.range == b.range && a.num_rays == b.num_rays && a.pos0 == b.pos0;
+      const int len = min((int)a.len, mp);
+      for (int k = 0; keep && k < len; ++k) keep = sp[lane * mp + k] == dp[lane * mp + k];
+    }
+  }
+  const uint64_t cmask = __ballot(cached);
+  uint64_t kmask = __ballot(keep);
+  if (kmask && __any(bytes_differ(sgrid, dgrid, p.RC, lane))) kmask = 0;
+  const uint64_t copy = cmask & ~kmask;
+  if (status_out && lane == 0) status_out[i] = copy == 0 && cmask != 0 ? 2 : (kmask == 0 ? 1 : 3);
+
+  copy16(p.scal + d, p.scal + s, (int)sizeof(EnvScalars) / 16, lane);
+  copy16(p.cams + (size_t)d * p.max_cams, p.cams + (size_t)s * p.max_cams, 2 * p.max_cams, lane);
+  copy16(dg, sg, 2 * mg, lane);
+  const int path_bytes = 2 * mg * mp;
+  copy_bytes(reinterpret_cast<uint8_t*>(dp), reinterpret_cast<const uint8_t*>(sp), path_bytes, path_bytes, lane);
+  if ((((uintptr_t)sgrid | (uintptr_t)dgrid | (uintptr_t)p.RC) & 15) == 0)
+    copy16(dgrid, sgrid, p.RC / 16, lane);
+  else
+    copy_bytes(dgrid, sgrid, p.RC, p.RC, lane);
+  copy16(p.stop + (size_t)d * p.stop_bytes, p.stop + (size_t)s * p.stop_bytes, p.stop_bytes / 16, lane);
+  constexpr int kBlock = kConePath * kConeSlots * kConeEntry;  // u16 per guard
+  constexpr int kRow16 = kConeSlots * kConeEntry * 2 / 16;     // 16-byte words per patrol index
+  for (uint64_t rest = copy; rest; rest &= rest - 1) {
+    const int g = __builtin_ctzll(rest);
+    const int rows = min(max((int)sg[g].len, 0), kConePath);
+    copy16x4(p.cones + ((size_t)d * mg + g) * kBlock, p.cones + ((size_t)s * mg + g) * kBlock, rows * kRow16, lane);
+  }
+}
+
+hipError_t launch_state_fork(const EnvParams& p, const int32_t* src_ids, const int32_t* dst_ids, int m,
+                             uint8_t* status_out, hipStream_t st) {
+  hipLaunchKernelGGL(state_fork_kernel, dim3(m), dim3(64), 0, st, p, src_ids, dst_ids, m, status_out);
+  return hipGetLastError();
 }
 
 hipError_t launch_state_save(const EnvParams& p, const int32_t* env_ids, int m, void* blobs, hipStream_t st) {

@@ -10,3 +10,4 @@ from .environment import EnvironmentConfig, HeistEnvironment  # noqa: F401
 from .vec_env import HeistEnv, LayoutBatch, PlanResult, STATUS_NAMES  # noqa: F401
 from .obs_compact import CompactObs  # noqa: F401
 from .env_state import EnvState  # noqa: F401
+from .search import LookaheadResult, exhaustive_lookahead  # noqa: F401

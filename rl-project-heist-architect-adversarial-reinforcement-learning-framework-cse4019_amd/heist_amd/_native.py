@@ -39,6 +39,7 @@ SIGNATURES = {
     "heist_state_bytes": (_i64, [_vp]),
     "heist_state_save": (_i, [_vp, _vp, _i, _vp, _vp]),
     "heist_state_load": (_i, [_vp, _vp, _i, _vp, _i, _vp, _vp, _vp]),
+    "heist_state_fork": (_i, [_vp, _vp, _vp, _i, _vp, _vp]),
     "heist_obs_record_bytes": (_i, [_i, _i]),
     "heist_obs_pack": (_i, [_vp, _i64, _i, _i, _i, _i, _vp, _vp]),
     "heist_obs_expand": (_i, [_vp, _i64, _vp, _vp, _i64, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -468,6 +468,24 @@ class HeistEnv:
                                                  nat.ptr(status), self._stream()), "heist_state_load")
         return status.view(torch.bool)
 
+    def fork_state(self, src_ids, dst_ids) -> torch.Tensor:
+        """heist_state_fork: env dst_ids[i] <- env src_ids[i] of this handle in one launch, with no
+        blob and no cone rebuild; a source may be named many times.  Returns status [m] uint8 on
+        this device: 0 rejected and dst untouched (an id out of range, src == dst, a dst named
+        twice or also named as a source), 1 forked with the guard cones copied, 2 forked with
+        the cones dst already held kept (dst had the source's layout), 3 some of each."""
+        src, dst = self._ids(src_ids, "fork_state"), self._ids(dst_ids, "fork_state")
+        if src is None or dst is None:
+            raise ValueError("fork_state: src_ids and dst_ids are required")
+        if src.numel() != dst.numel():
+            raise ValueError("fork_state: %d source ids for %d destination ids" % (src.numel(), dst.numel()))
+        m = int(src.numel())
+        status = torch.zeros(m, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_state_fork(self._h, nat.ptr(src), nat.ptr(dst), m, nat.ptr(status),
+                                                 self._stream()), "heist_state_fork")
+        return status
+
     # -- compact observation records (obs_compact.CompactObs) ---------------------------
     def grid_snapshot(self) -> torch.Tensor:
         """The envs' grids [N, R, C] int8 as they stand now (heist_export's grid alone): what
