@@ -274,6 +274,39 @@ int heist_plan_supported(heist_t h);
 int heist_plan(heist_t h, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
                heist_stream_t stream);
 
+/* Planner field, no reference counterpart: heist_plan's answer for every cell of every env at once
+ * -- the exact value function of the Solver's game against the emitters' schedule.  Env e runs
+ * HK = min(horizon, max_steps - tick[e]) ticks, 0 for an env already done.  With
+ *   vis_k      = heist_plan's vis_k, k = 1 .. HK,
+ *   move(x, a) = x + delta(a) if that cell is inside the grid and not a wall tile, else x
+ *                (0 WAIT, 1 UP, 2 DOWN, 3 LEFT, 4 RIGHT),
+ *   togo_HK[x] = none for every cell,
+ * and for k = HK-1 .. 0 and every non-wall cell x, the vault's included,
+ *   togo_k[x]  = the minimum over the five actions a, y = move(x, a), of
+ *                none                if y is in vis_{k+1},
+ *                1                   if y is the vault,
+ *                none                if togo_{k+1}[y] is none,
+ *                togo_{k+1}[y] + 1   otherwise;
+ * wall cells are none, and none is stored as -1.  togo_0[x] is what heist_plan returns as ticks_out
+ * for this env with the Solver's cell set to x, the max_steps rule included (an arrival on the
+ * tick that times out counts); every cell of a done env is -1.
+ *   togo_out       [N][R*C] int16: togo_0, in 1 .. 1024 or -1.
+ *   action_out     [N][R*C] int8: the lowest action that attains togo_0[x], -1 where togo_0[x] is -1.
+ *   vis_out        [horizon][N][W] uint32, W = heist_obs_record_bytes(rows, cols) / 4, 16-byte
+ *                  aligned, required (it is also the backward sweep's history): row k-1 holds vis_k
+ *                  in the record's bit order (bit i of word j is cell 32 j + i), bits past R*C and
+ *                  words past ceil(R*C/32) are 0, rows k >= HK are 0.
+ *   togo_ticks_out [horizon][N][R*C] int16 or NULL, 2-byte aligned: row k holds togo_k for k < HK
+ *                  (row 0 equals togo_out), rows k >= HK are -1.
+ * The launch only reads the env, as heist_plan does: state, shared-fan bookkeeping, counters and
+ * stamps are untouched.
+ * heist_plan_field_supported: heist_plan_supported's value.
+ * HEIST_EINVAL: horizon outside 1..1024, a NULL togo_out, action_out or vis_out, vis_out not
+ * 16-byte aligned, a probe mode armed (HEIST_PROBE_MODE), heist_plan_field_supported 0. */
+int heist_plan_field_supported(heist_t h);
+int heist_plan_field(heist_t h, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
+                     int16_t* togo_ticks_out, heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

@@ -32,6 +32,8 @@ hipError_t launch_step_multi_records(const EnvParams& p, int K, const int64_t* a
 hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,
                          double* guard_heading, hipStream_t st);
 bool plan_variant_exists(const EnvParams& p);
+hipError_t launch_plan_field(const EnvParams& p, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
+                             int16_t* togo_ticks_out, hipStream_t st);
 hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
                        hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
@@ -567,6 +569,29 @@ int heist_plan(heist_t h, int horizon, int32_t* ticks_out, int64_t* actions_out,
   q.fan_base = 0;
   return check_hip(heist::launch_plan(q, horizon, ticks_out, actions_out, reach_out, (hipStream_t)stream),
                    "heist_plan");
+}
+
+int heist_plan_field_supported(heist_t h) { return heist_plan_supported(h); }
+
+int heist_plan_field(heist_t h, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
+                     int16_t* togo_ticks_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_field: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(togo_out && action_out && vis_out, "heist_plan_field: null output");
+  HEIST_REQUIRE(((uintptr_t)vis_out & 15) == 0, "heist_plan_field: vis_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)togo_out & 1) == 0 && ((uintptr_t)togo_ticks_out & 1) == 0,
+                "heist_plan_field: togo_out / togo_ticks_out misaligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan_field: a probe mode is armed (HEIST_PROBE_MODE)");
+  HEIST_REQUIRE(heist::plan_variant_exists(h->p), "heist_plan_field: no planner kernel for this handle "
+                                                  "(heist_plan_field_supported is 0)");
+  // the launch's own EnvParams, as heist_plan's: no shared fan (every camera cast live)
+  EnvParams q = h->p;
+  q.fan_on = 0;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  return check_hip(heist::launch_plan_field(q, horizon, togo_out, action_out, vis_out, togo_ticks_out,
+                                            (hipStream_t)stream),
+                   "heist_plan_field");
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

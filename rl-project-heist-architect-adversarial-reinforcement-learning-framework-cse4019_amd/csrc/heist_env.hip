@@ -2464,6 +2464,239 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ
 }
 
 // ---------------------------------------------------------------------------
+// Planner field (heist_plan_field): fewest undetected ticks to the vault from every cell
+// ---------------------------------------------------------------------------
+//
+// The planner's question for every cell at once, as the backward recurrence over the same
+// visibility planes (include/heist.h): togo_HK = none, and for k = HK - 1 .. 0
+//   togo_k[x] = min over the five actions a, y = move(x, a), of
+//               none if y in vis_{k+1}; 1 if y is the vault; togo_{k+1}[y] + 1 (none stays none).
+// Forward pass: plan_kernel's prologue and tick without the DP step and without an exit -- all HK
+// ticks run, and each tick's ray plane | guard plane is ballot-packed, 64 cells per wave pass,
+// straight into the env's row of vis_out (row k - 1 = vis_k, the record's bit order).  Backward
+// pass, after a fence and a barrier: the env's own rows come back with agent-scope loads, one
+// row ahead of its use, into two LDS rows (tick parity); togo_{k+1} and togo_k are two uint16
+// [R C] arrays in LDS (none = 0xFFFF, the int16 -1 of the outputs as it stands).  One cell per
+// lane, the planner's row / column tests, the five candidates in action order with a strict
+// less-than (the first minimum wins: a blocked move is a stay and never beats WAIT); one
+// barrier per k.  Every step's array goes out to togo_ticks_out when given, step 0's to
+// togo_out with its actions.
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_field_kernel(
+    EnvParams p, int H, int16_t* __restrict__ togo_out, int8_t* __restrict__ action_out, uint32_t* vis_out,
+    int16_t* __restrict__ togo_ticks_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr bool SOLO = W == 1;
+  constexpr uint32_t kNone = 0xFFFFu;
+  const int e = block_env(p);
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, N = p.n_envs, C = p.C;
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // cached guard cones of the tick, vis geometry
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6;
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;  // the record's words (obs_record_words)
+  uint16_t* togo = reinterpret_cast<uint16_t*>(uq + 128 * W);      // [2][RC] ticks to go, tick parity
+  uint32_t* vrow = reinterpret_cast<uint32_t*>(togo + 2 * RC);     // [2][nvis] visibility rows, tick parity
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;
+    prefetch<NT>(p, e, eb, L, raw);
+    if (t < n_slot) rec[t] = raw;
+  }
+  for (int i = t; i < path_words; i += NT) L.path[i] = eb.paths[i];
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  const int g = t - mc;
+  const bool live_cam = t < s.n_cams, live_guard = g >= 0 && g < s.n_guards;
+  bool cached = false;
+  uint4 ca = make_uint4(0u, 0u, 0u, 0u), cb = ca;
+  // a cached guard's cone entry for the coming tick, loaded one tick ahead (step_multi_body)
+  auto next_entry = [&](const Guard& gd) {
+    int idx = gd.idx, slot = gd.hslot;
+    if (gd.len >= 2) {
+      idx += gd.step;
+      if (idx >= gd.len) idx -= gd.len;
+      slot = gd.nslot;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(eb.cones + cone_off(g, idx, slot));
+    ca = src[0];
+    cb = src[1];
+  };
+  auto take_entry = [&]() {
+    Guard gd = as_guard(rec[t]);
+    gd.nslot = (uint8_t)(cb.w >> 16);  // row 15
+    rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+    uint4* dst = reinterpret_cast<uint4*>(L.cone + 16 * g);
+    dst[0] = ca;
+    dst[1] = cb;
+  };
+  __syncthreads();  // records in LDS
+  if (HK > 0 && live_guard) {
+    const Guard gd = as_guard(rec[t]);
+    cached = gd.hslot != kUncached;
+    if (cached) next_entry(gd);
+  }
+
+  // cell / C as a multiply-shift (plan_kernel)
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+
+  // ---- forward: vis_1 .. vis_HK into the env's rows of vis_out
+  for (int k = 1; k <= HK; ++k) {
+    // (the barrier that closed the previous tick's pack also closed its readers of vis / em / cones)
+    Emit E;
+    E.kind = -1;
+    if (w0) {
+      // cameras rotate, guards patrol (security.py:49-51, :145-159), unconditionally
+      if (live_cam) {
+        Cam cm = as_cam(rec[t]);
+        cm.heading = py_mod360(cm.heading + cm.speed * 1.0);
+        rec[t] = __builtin_bit_cast(EmitterRaw, cm);
+        E = cam_emit(cm);
+      } else if (live_guard) {
+        Guard gd = as_guard(rec[t]);
+        const bool moves = gd.len >= 2;
+        int nidx = gd.idx;
+        if (moves) {
+          nidx += gd.step;
+          if (nidx >= gd.len) nidx -= gd.len;
+        }
+        const uint16_t np = moves ? L.path[__umul24((uint32_t)g, (uint32_t)p.max_path) + (uint32_t)nidx] : gd.pos;
+        if (cached) {
+          if (moves) gd.hslot = gd.nslot;
+        } else if (moves) {
+          gd.heading = guard_heading_after(p, unpack_r(np) - unpack_r(gd.pos), unpack_c(np) - unpack_c(gd.pos),
+                                           gd.heading);
+        }
+        gd.idx = (int16_t)nidx;
+        gd.pos = np;
+        rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+        E = guard_emit(gd);
+        if (cached && !SOLO) take_entry();
+      }
+      publish_emitters(L, E, n_slot);
+    }
+    clear_planes<NT>(p, L, gvis, true);
+    __syncthreads();  // emitter table, cone rows, cleared planes
+    if (live_guard && E.kind == 1) L.vis[L.at(E.row, E.col)] = 1;  // visibility.py:59
+    cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+    if (SOLO && cached) take_entry();
+    stamp_guard_cones<NT>(L, gvis, mc, mg, 0);
+    __syncthreads();  // planes complete
+
+    // the tick's plane, 64 cells per ballot, as the two words of its chunk; the pad words are 0
+    uint32_t* row = vis_out + ((size_t)(k - 1) * N + e) * WR;
+    for (int ch = wave; ch < n_chunk; ch += W) {
+      const int cell = 64 * ch + lane;
+      bool on = false;
+      if (cell < RC) {
+        const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+        const int a = L.at(r, c);
+        on = (L.vis[a] | gvis[a]) != 0;
+      }
+      const unsigned long long m = __ballot(on);
+      if (lane < 2 && 2 * ch + lane < WR) row[2 * ch + lane] = (uint32_t)(m >> (32 * lane));
+    }
+    for (int i = 2 * n_chunk + t; i < WR; i += NT) row[i] = 0u;
+    if (w0 && live_guard && cached && k < HK) next_entry(as_guard(rec[t]));  // lands during the next tick
+    __syncthreads();  // the planes' readers are done
+  }
+
+  // the rows this env did not run, 16 bytes per store (WR is a multiple of 4, vis_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - HK) * q4; i += NT) {
+      const int r = HK + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(vis_out + ((size_t)r * N + e) * WR)[q] = z;
+    }
+  }
+  if (togo_ticks_out)
+    for (int k = HK; k < H; ++k) {
+      int16_t* trow = togo_ticks_out + ((size_t)k * N + e) * RC;
+      for (int x = t; x < RC; x += NT) trow[x] = (int16_t)-1;
+    }
+  if (HK == 0) {  // block-uniform: an env already done (or past max_steps) has no value anywhere
+    for (int x = t; x < RC; x += NT) {
+      togo_out[(size_t)e * RC + x] = (int16_t)-1;
+      action_out[(size_t)e * RC + x] = (int8_t)-1;
+    }
+    return;
+  }
+
+  // ---- backward: togo_{HK-1} .. togo_0
+  __threadfence();  // this env's rows visible to the lanes that read them back
+  for (int x = t; x < RC; x += NT) togo[(HK & 1) * RC + x] = (uint16_t)kNone;  // togo_HK
+  // row k of vis_out is vis_{k+1}; nvis <= NT for every instance (launch_plan_field checks it)
+  auto load_row = [&](int k) {
+    return __hip_atomic_load(vis_out + ((size_t)k * N + e) * WR + (t < nvis ? t : 0), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  };
+  __syncthreads();
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  const int vcell = p.vr * C + p.vc;
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;          // vis_{k+1}
+    const uint16_t* nxt = togo + ((k + 1) & 1) * RC;     // togo_{k+1}
+    uint16_t* cur = togo + (k & 1) * RC;                 // togo_k
+    int16_t* trow = togo_ticks_out ? togo_ticks_out + ((size_t)k * N + e) * RC : nullptr;
+    for (int x = t; x < RC; x += NT) {
+      uint32_t best = kNone;
+      int act = -1;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        auto val = [&](int y) -> uint32_t {
+          if ((vk[y >> 5] >> (y & 31)) & 1u) return kNone;
+          if (y == vcell) return 1u;
+          const uint32_t v = nxt[y];
+          return v == kNone ? kNone : v + 1u;
+        };
+        auto moved = [&](bool inside, int y) { return inside && L.grid[y] != kWall ? y : x; };
+        best = val(x);
+        act = 0;
+        uint32_t v = val(moved(r > 0, x - C));
+        if (v < best) best = v, act = 1;
+        v = val(moved(r + 1 < p.R, x + C));
+        if (v < best) best = v, act = 2;
+        v = val(moved(c > 0, x - 1));
+        if (v < best) best = v, act = 3;
+        v = val(moved(c + 1 < C, x + 1));
+        if (v < best) best = v, act = 4;
+        if (best == kNone) act = -1;
+      }
+      cur[x] = (uint16_t)best;
+      if (trow) trow[x] = (int16_t)(uint16_t)best;
+      if (k == 0) {
+        togo_out[(size_t)e * RC + x] = (int16_t)(uint16_t)best;
+        action_out[(size_t)e * RC + x] = (int8_t)act;
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // togo_k and vis_k complete; their previous holders' readers are done
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean K-tick kernel (heist_step_multi, one wave per env, grids up to 20 x 20)
 // ---------------------------------------------------------------------------
 //
@@ -4087,6 +4320,29 @@ hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int6
   }
   HEIST_MULTI_VARIANTS(HEIST_PLAN_CASE)
 #undef HEIST_PLAN_CASE
+  return hipErrorInvalidValue;  // not reached
+}
+
+// heist_plan_field: plan_kernel's instances.  LDS: the planner's without its reach sets and
+// flags, plus the two uint16 [R C] arrays of ticks to go and the two visibility rows.
+hipError_t launch_plan_field(const EnvParams& p, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
+                             int16_t* togo_ticks_out, hipStream_t st) {
+  const int nvis = (p.RC + 31) >> 5;
+  // the backward sweep fetches a visibility row with one word per lane
+  if (!plan_variant_exists(p) || nvis > 64 * p.multi_waves) return hipErrorInvalidValue;
+  const int n_slot = p.max_cams + p.max_guards;
+  const size_t lds =
+      align16(env_lds_bytes(p.R, p.C, n_slot, p.max_guards * p.max_path, p.vis_gap, p.multi_waves, p.max_guards)) +
+      32 * (size_t)n_slot + (size_t)p.vis_gap + align16(sizeof(TieBuckets)) + 1024 * (size_t)p.multi_waves +
+      4 * (size_t)p.RC + 8 * (size_t)nvis;
+#define HEIST_FIELD_CASE(W, D)                                                                                   \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                    \
+    hipLaunchKernelGGL((plan_field_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, horizon, togo_out,   \
+                       action_out, vis_out, togo_ticks_out);                                                     \
+    return hipGetLastError();                                                                                    \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_FIELD_CASE)
+#undef HEIST_FIELD_CASE
   return hipErrorInvalidValue;  // not reached
 }
 

@@ -3,6 +3,10 @@ env, evaluated by forking the roots on the device (HeistEnv.fork_state) and one 
 
 The index math is in three pure functions (no device needed): lookahead_workers picks and checks
 the worker envs, action_table builds the launch's actions, select_best picks each root's winner.
+
+follow_field and expert_labels read a planner field (HeistEnv.plan_field(all_ticks=True)): the
+field's own plan from any cell, and the exact ticks to go and optimal action of every state a
+rollout visited.  Both are pure torch and run wherever the field's tensors live.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -67,6 +71,92 @@ def select_best(returns: torch.Tensor) -> torch.Tensor:
     j = torch.arange(B, dtype=torch.int64, device=returns.device).expand_as(returns)
     top = returns == returns.max(dim=1, keepdim=True).values
     return torch.where(top, j, torch.full_like(j, B)).min(dim=1).values
+
+
+DELTA = ((0, 0), (-1, 0), (1, 0), (0, -1), (0, 1))  # the actions' (dr, dc)
+
+
+def _field_action(field, k: int, r: torch.Tensor, c: torch.Tensor):
+    """The planner field's rule at tick k for env i's Solver on cell (r[i], c[i]): (togo [N] int64,
+    action [N] int64, next r, next c).  action is the lowest a for which y = move(x, a) is not in
+    vis_{k+1} and y is the vault or togo_{k+1}[y] == togo_k[x] - 1; -1 (and the cell kept) where
+    togo_k[x] is -1.  A move into a wall or off the grid is a stay, which WAIT already covers, so
+    only real moves are tried for a = 1 .. 4 (a wall's togo is -1: it never matches)."""
+    tg, vis = field.togo_ticks, field.vis
+    H, N, R, C = tg.shape
+    vr, vc = field.vault
+    n = torch.arange(N, device=tg.device)
+    r, c = r.long(), c.long()
+    cur = tg[k, n, r, c].long()
+    act = torch.full_like(cur, -1)
+    nr, nc = r.clone(), c.clone()
+    for a in range(N_ACTIONS - 1, -1, -1):
+        yr, yc = r + DELTA[a][0], c + DELTA[a][1]
+        inside = (yr >= 0) & (yr < R) & (yc >= 0) & (yc < C)
+        yr, yc = yr.clamp(0, R - 1), yc.clamp(0, C - 1)
+        cell = yr * C + yc
+        seen = ((vis[k, n, cell >> 5].long() >> (cell & 31)) & 1).bool()
+        nxt = tg[k + 1, n, yr, yc].long() if k + 1 < H else torch.full_like(cur, -1)
+        ok = inside & ~seen & (cur > 0) & (((yr == vr) & (yc == vc)) | ((nxt > 0) & (nxt == cur - 1)))
+        act = torch.where(ok, torch.full_like(act, a), act)
+        nr, nc = torch.where(ok, yr, nr), torch.where(ok, yc, nc)
+    return cur, act, nr, nc
+
+
+def _need_all_ticks(field, what):
+    if field.togo_ticks is None:
+        raise ValueError("%s: the field has no togo_ticks (plan_field(all_ticks=True))" % what)
+    if field.vault is None:
+        raise ValueError("%s: the field does not name its vault" % what)
+
+
+def follow_field(field, pos_r, pos_c):
+    """The field's own plan from each env's cell (pos_r, pos_c: [N]): (actions [H, N] int64,
+    ticks [N] int32).  At tick k the Solver takes the lowest optimal action (_field_action) until
+    it stands on the vault; the rows after that, and every row of an env whose cell has no value,
+    are 0 -- feed the tensor (or its first rows) to step_multi(auto_reset=False).  ticks is togo_0
+    at the start cell.  Pure torch: runs on the device of the field's tensors, CPU included."""
+    _need_all_ticks(field, "follow_field")
+    tg = field.togo_ticks
+    H, N = tg.shape[:2]
+    dev = tg.device
+    r = torch.as_tensor(pos_r, device=dev).long().reshape(N)
+    c = torch.as_tensor(pos_c, device=dev).long().reshape(N)
+    actions = torch.zeros((H, N), dtype=torch.int64, device=dev)
+    ticks = tg[0, torch.arange(N, device=dev), r, c].to(torch.int32)
+    alive = ticks > 0
+    vr, vc = field.vault
+    for k in range(H):
+        if not bool(alive.any()):
+            break
+        _, act, nr, nc = _field_action(field, k, r, c)
+        go = alive & (act >= 0)
+        actions[k] = torch.where(go, act, torch.zeros_like(act))
+        r, c = torch.where(go, nr, r), torch.where(go, nc, c)
+        alive = go & ~((r == vr) & (c == vc))
+    return actions, ticks
+
+
+def expert_labels(field, pos_r, pos_c):
+    """Exact labels along a rollout: pos_r, pos_c [K, N] with K <= H, row k the Solver's cell after
+    k ticks (row 0 the cell now, rows 1 .. the position word of a step_multi_records launch played
+    without auto-reset).  Returns (togo [K, N] int16, action [K, N] int8): the fewest ticks to go
+    from that state and the lowest optimal action in it (follow_field's rule), -1 where the vault
+    is out of reach.  Pure torch."""
+    _need_all_ticks(field, "expert_labels")
+    tg = field.togo_ticks
+    H, N = tg.shape[:2]
+    dev = tg.device
+    pr, pc = torch.as_tensor(pos_r, device=dev).long(), torch.as_tensor(pos_c, device=dev).long()
+    if pr.dim() != 2 or pr.shape != pc.shape or pr.shape[1] != N or pr.shape[0] > H:
+        raise ValueError("expert_labels: cells must be [K, %d] with K <= %d" % (N, H))
+    K = pr.shape[0]
+    togo = torch.empty((K, N), dtype=torch.int16, device=dev)
+    action = torch.empty((K, N), dtype=torch.int8, device=dev)
+    for k in range(K):
+        cur, act, _, _ = _field_action(field, k, pr[k], pc[k])
+        togo[k], action[k] = cur.to(torch.int16), act.to(torch.int8)
+    return togo, action
 
 
 @dataclass

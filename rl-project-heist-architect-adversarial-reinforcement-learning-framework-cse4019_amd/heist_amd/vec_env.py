@@ -120,6 +120,35 @@ class PlanResult:
         return bits.reshape(w.shape[0], -1)[:, :self.rows * self.cols].reshape(-1, self.rows, self.cols).bool()
 
 
+@dataclass
+class PlanField:
+    """HeistEnv.plan_field's output (heist_plan_field, include/heist.h), device tensors:
+    togo [N, R, C] int16 -- the fewest ticks to a clean vault arrival from every cell as the env
+        stands now (what plan() gives with the Solver on that cell), -1 where there is none;
+    action [N, R, C] int8 -- the lowest action that attains it, -1 where togo is -1;
+    vis [H, N, W] int32 -- row k - 1: the visibility plane of the env's k-th tick from now, in the
+        compact record's bit order (bit i of word j is cell 32 j + i), 0 past the env's ticks;
+    togo_ticks [H, N, R, C] int16 or None -- row k: the same field k ticks from now (row 0 equals
+        togo), -1 past the env's ticks; with all_ticks=True only;
+    vault -- the vault's (row, col), which heist_amd.search.follow_field / expert_labels need."""
+    togo: torch.Tensor
+    action: torch.Tensor
+    vis: torch.Tensor
+    togo_ticks: Optional[torch.Tensor]
+    rows: int
+    cols: int
+    vault: Optional[Tuple[int, int]] = None
+
+    def vis_mask(self, k: int) -> torch.Tensor:
+        """vis_k for k = 1 .. H as bool [N, R, C]."""
+        if not 1 <= k <= self.vis.shape[0]:
+            raise IndexError("vis_mask: k must be 1 .. %d" % self.vis.shape[0])
+        w = self.vis[k - 1]
+        sh = torch.arange(32, device=w.device, dtype=torch.int32)
+        bits = (w.unsqueeze(-1) >> sh) & 1
+        return bits.reshape(w.shape[0], -1)[:, :self.rows * self.cols].reshape(-1, self.rows, self.cols).bool()
+
+
 class HeistEnv:
     """Batched HeistEnvironment on one HIP device.
 
@@ -365,6 +394,35 @@ class HeistEnv:
             nat.check(nat.lib().heist_plan(self._h, H, nat.ptr(ticks), nat.ptr(actions), nat.ptr(reach), self._stream()),
                       "heist_plan")
         return PlanResult(ticks, actions, reach, self.rows, self.cols)
+
+    # -- planner field (heist_plan_field) ----------------------------------------------------
+    @property
+    def plan_field_supported(self) -> int:
+        """heist_plan_field_supported: 1 when plan_field() has a kernel for this handle."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_field_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_field_supported")
+        return d
+
+    def plan_field(self, horizon: Optional[int] = None, all_ticks: bool = False) -> "PlanField":
+        """heist_plan_field: for every env as it stands and every cell, the fewest ticks in which a
+        Solver on that cell can reach the vault undetected and the lowest action that starts such
+        a path, plus the visibility plane of every coming tick; with all_ticks the same field for
+        every later tick of the horizon (heist_amd.search.follow_field / expert_labels read it).
+        horizon: ticks to look ahead (default config.max_steps, at most 1024); an env runs
+        min(horizon, max_steps - tick).  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        kw = dict(device=self.device)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        togo = torch.empty((n, R, C), dtype=torch.int16, **kw)
+        action = torch.empty((n, R, C), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, record_words(R, C)), dtype=torch.int32, **kw)
+        ticks = torch.empty((h, n, R, C), dtype=torch.int16, **kw) if all_ticks else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_field(self._h, H, nat.ptr(togo), nat.ptr(action), nat.ptr(vis), nat.ptr(ticks),
+                                                 self._stream()), "heist_plan_field")
+        return PlanField(togo, action, vis, ticks, R, C, tuple(int(v) for v in self.config.vault_pos))
 
     def step_multi_raw(self, K: int, actions: torch.Tensor, obs_out: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, status: torch.Tensor, auto_reset: bool = True) -> None:

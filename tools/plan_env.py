@@ -9,6 +9,10 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # Manhattan distance in ticks, none casts a ray -- the cost
                                                  # of the prologue, the DP step and the row stores alone
   python tools/plan_env.py --ckpt checkpoints/architect_ep500.pt
+  python tools/plan_env.py --field               # the planner field (heist_plan_field, HeistEnv.plan_field) next to
+                                                 # heist_plan on the three batches above, one JSON line each,
+                                                 # also written to profiles/plan_field.log (--out)
+  python tools/plan_env.py --field --all-ticks   # ... and the launch that writes every tick's field as well
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -49,6 +53,60 @@ def timed(dev, fn, warmup, runs):
     return ms
 
 
+def make_env(args, kind, dev):
+    """A reset handle of args.envs envs under `kind` layouts (architect, synthetic, empty)."""
+    R, N, budget = args.grid, args.envs, args.budget
+    cfg = EnvironmentConfig(grid_rows=R, grid_cols=R, max_steps=args.max_steps, architect_budget=budget)
+    env = HeistEnv(N, cfg, max_cams=max(1, budget // 3), max_guards=max(1, budget // 5), max_path=16, device=dev,
+                   auto_reset=True)
+    if kind == "architect":
+        bench.architect_layouts(env, budget, seed=args.seed, ckpt=args.ckpt)
+    elif kind == "synthetic":
+        valid_synthetic_layouts(env, budget, seed=args.seed)
+    else:
+        env.set_layouts([([], [], [])] * N, budget=budget)
+    env.reset()
+    return env
+
+
+def field_table(args, dev):
+    """heist_plan_field next to heist_plan, same handle, same process, same state (both only read
+    the envs): one JSON line per batch."""
+    H = min(args.horizon or args.max_steps, 1024)
+    lines = []
+    for kind in ("architect", "empty", "synthetic"):
+        env = make_env(args, kind, dev)
+        kc = env.kernel_config()
+        assert env.plan_field_supported == 1, kc
+        res, f = env.plan(H), env.plan_field(H)
+        sr, sc = env.config.start_pos
+        ok = res.ticks > 0
+        walls = env.grid_snapshot() == 1
+        out = {"config": "%dx%d" % (args.grid, args.grid), "envs": args.envs, "layouts": kind, "horizon": H,
+               "multi_waves": kc["multi_waves"], "solvable_frac": float(ok.float().mean()),
+               "field_at_start_equals_plan": bool(torch.equal(f.togo[:, sr, sc].int(), res.ticks)),
+               "winnable_cell_frac": float((f.togo > 0).sum()) / float((~walls).sum()),
+               "togo_max": int(f.togo.max())}
+        p = statistics.median(timed(dev, lambda: env.plan(H), args.warmup, args.runs))
+        ms = timed(dev, lambda: env.plan_field(H), args.warmup, args.runs)
+        m = statistics.median(ms)
+        out["plan_launch_ms_median"] = p
+        out["field"] = {"launch_ms_median": m, "launch_ms": ms, "us_per_tick_of_horizon": m / H * 1e3,
+                        "ns_per_env_tick": m * 1e6 / (H * args.envs), "over_plan": m / p}
+        if args.all_ticks:
+            ms = timed(dev, lambda: env.plan_field(H, all_ticks=True), args.warmup, args.runs)
+            a = statistics.median(ms)
+            out["field_all_ticks"] = {"launch_ms_median": a, "launch_ms": ms, "over_field": a / m,
+                                      "togo_ticks_mb": H * args.envs * args.grid * args.grid * 2 / 1e6}
+        env.close()
+        lines.append(json.dumps(out))
+        print(lines[-1], flush=True)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as fh:
+        fh.write("$ python tools/plan_env.py --field%s\n" % (" --all-ticks" if args.all_ticks else ""))
+        fh.write("\n".join(lines) + "\n")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--envs", type=int, default=4096)
@@ -61,9 +119,14 @@ def main(argv=None):
     ap.add_argument("--seed", type=int, default=1234)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=7)
+    ap.add_argument("--field", action="store_true", help="time heist_plan_field next to heist_plan on all three batches")
+    ap.add_argument("--all-ticks", action="store_true", help="with --field: also the launch that writes togo_ticks")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_field.log"), help="--field's log")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.field:
+        return field_table(args, dev)
     R, N, budget = args.grid, args.envs, args.budget
     cfg = EnvironmentConfig(grid_rows=R, grid_cols=R, max_steps=args.max_steps, architect_budget=budget)
     env = HeistEnv(N, cfg, max_cams=max(1, budget // 3), max_guards=max(1, budget // 5), max_path=16, device=dev,
