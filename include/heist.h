@@ -307,6 +307,54 @@ int heist_plan_field_supported(heist_t h);
 int heist_plan_field(heist_t h, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
                      int16_t* togo_ticks_out, heist_stream_t stream);
 
+/* Planner value, no reference counterpart: the exact optimal discounted return of the Solver from
+ * every cell of every env -- heist_plan_field's recurrence under the env's own step reward
+ * (environment.py:235, :261-297) instead of a tick count.  Env e runs HK = min(horizon,
+ * max_steps - tick[e]) steps, 0 for an env already done.  With vis_k and move(x, a) as in
+ * heist_plan_field, dist(x) the Manhattan distance from x to the vault, D0 the env's initial_dist,
+ * r_step, r_detect, r_vault the handle's reward_consts, tick the env's tick and
+ *   V_HK[x] = 0.0 for every cell,
+ * for k = HK-1 .. 0, every non-wall cell x (the vault's included) and a = 0 .. 4 in order, with
+ * y = move(x, a) and curr = dist(y), each line one IEEE double operation, none contracted:
+ *   rew = r_step
+ *   rew = rew + (double)(dist(x) - curr) * 0.1
+ *   if curr <= 3 and D0 > 3:   rew = rew + 0.05 * (double)(3 - curr)
+ *   seen = y in vis_{k+1};     if seen:       rew = rew + r_detect
+ *                              if y == vault: rew = rew + r_vault          (both may apply)
+ *   last = tick + k + 1 >= max_steps
+ *   if last: frac = 1.0 - (double)curr / (double)max(D0, 1); if frac < 0: frac = 0;
+ *            rew = rew + frac * 2.0
+ *   q = (seen or y == vault or last) ? rew : rew + gamma * V_{k+1}[y]
+ * V_k[x] is the maximum q under a strict greater-than (the first maximum stays: a blocked move
+ * ties with WAIT and is never chosen) and the action is that first a.  Wall cells hold 0.0 and -1;
+ * every cell of an env with HK = 0 holds 0.0 and -1.
+ * V_0[pos] is the largest value, over the action sequences heist_step_multi(..., auto_reset = 0)
+ * can be fed for HK ticks, of the reward64 of tick k times gamma^k summed from the back
+ * (r_k + gamma * (...)), for an env whose prev_dist equals dist(pos): heist_reset and heist_step
+ * always leave it so, only an edited state blob does not.  With horizon < max_steps - tick it is
+ * the horizon-truncated return.
+ *   value_out        [N][R*C] float64, 8-byte aligned: V_0.
+ *   action_out       [N][R*C] int8: the action at k = 0.
+ *   vis_out          [horizon][N][W] uint32, 16-byte aligned, required: exactly heist_plan_field's
+ *                    vis_out, padding and rows k >= HK included.
+ *   value_ticks_out  [horizon][N][R*C] float64 or NULL, 8-byte aligned: row k holds V_k for k < HK
+ *                    (row 0 equals value_out), rows k >= HK are 0.0.
+ *   action_ticks_out [horizon][N][R*C] int8 or NULL: row k holds the actions of step k, rows
+ *                    k >= HK are -1.  The two optional outputs are independent of each other.
+ * The launch only reads the env, as heist_plan_field does.
+ * heist_plan_value_supported: 1 where heist_plan_field_supported is 1, one word per lane fetches a
+ *   visibility row and the kernel's LDS -- heist_plan_field's plus 12 R C bytes: two float64
+ *   [R*C] arrays -- fits the 64 KB a workgroup gets by default: every grid up to 32 x 32 at 1, 2 and
+ *   4 K-tick waves.  The dynamic LDS limit is not raised: at 64 x 64 the two arrays alone are
+ *   64 KB and the value is 0.  -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, gamma not finite or outside [0, 1], a NULL value_out,
+ * action_out or vis_out, vis_out not 16-byte aligned, value_out or value_ticks_out not 8-byte
+ * aligned, a probe mode armed (HEIST_PROBE_MODE), heist_plan_value_supported 0. */
+int heist_plan_value_supported(heist_t h);
+int heist_plan_value(heist_t h, int horizon, double gamma, double* value_out, int8_t* action_out,
+                     uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out,
+                     heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

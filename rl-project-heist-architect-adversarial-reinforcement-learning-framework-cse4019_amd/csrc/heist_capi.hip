@@ -34,6 +34,9 @@ hipError_t launch_export(const EnvParams& p, int32_t* scalars, int8_t* grid, dou
 bool plan_variant_exists(const EnvParams& p);
 hipError_t launch_plan_field(const EnvParams& p, int horizon, int16_t* togo_out, int8_t* action_out, uint32_t* vis_out,
                              int16_t* togo_ticks_out, hipStream_t st);
+bool plan_value_variant_exists(const EnvParams& p);
+hipError_t launch_plan_value(const EnvParams& p, int horizon, double gamma, double* value_out, int8_t* action_out,
+                             uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out, hipStream_t st);
 hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
                        hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
@@ -592,6 +595,33 @@ int heist_plan_field(heist_t h, int horizon, int16_t* togo_out, int8_t* action_o
   return check_hip(heist::launch_plan_field(q, horizon, togo_out, action_out, vis_out, togo_ticks_out,
                                             (hipStream_t)stream),
                    "heist_plan_field");
+}
+
+int heist_plan_value_supported(heist_t h) {
+  if (check_handle(h)) return -1;
+  return heist::plan_value_variant_exists(h->p) ? 1 : 0;
+}
+
+int heist_plan_value(heist_t h, int horizon, double gamma, double* value_out, int8_t* action_out, uint32_t* vis_out,
+                     double* value_ticks_out, int8_t* action_ticks_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_value: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "heist_plan_value: need 0 <= gamma <= 1");
+  HEIST_REQUIRE(value_out && action_out && vis_out, "heist_plan_value: null output");
+  HEIST_REQUIRE(((uintptr_t)vis_out & 15) == 0, "heist_plan_value: vis_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)value_out & 7) == 0 && ((uintptr_t)value_ticks_out & 7) == 0,
+                "heist_plan_value: value_out / value_ticks_out must be 8-byte aligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan_value: a probe mode is armed (HEIST_PROBE_MODE)");
+  HEIST_REQUIRE(heist::plan_value_variant_exists(h->p), "heist_plan_value: no value kernel for this handle "
+                                                        "(heist_plan_value_supported is 0)");
+  // the launch's own EnvParams, as heist_plan's: no shared fan (every camera cast live)
+  EnvParams q = h->p;
+  q.fan_on = 0;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  return check_hip(heist::launch_plan_value(q, horizon, gamma, value_out, action_out, vis_out, value_ticks_out,
+                                            action_ticks_out, (hipStream_t)stream),
+                   "heist_plan_value");
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

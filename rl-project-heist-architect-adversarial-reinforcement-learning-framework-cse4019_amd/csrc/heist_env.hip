@@ -2697,6 +2697,263 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ
 }
 
 // ---------------------------------------------------------------------------
+// Planner value (heist_plan_value): the optimal discounted Solver return from every cell
+// ---------------------------------------------------------------------------
+//
+// The field's question under the env's real reward (include/heist.h): the step reward depends on
+// the cell before, the cell after, whether that cell is seen on that tick, the tick number and
+// the env's initial_dist alone (prev_dist is the Manhattan distance of the cell the Solver stands
+// on), so with V_HK = 0 and for k = HK - 1 .. 0
+//   V_k[x] = max over the five actions a, y = move(x, a), of
+//            rew(x, y, k)                       if y in vis_{k+1}, y is the vault or the tick times out,
+//            rew(x, y, k) + gamma V_{k+1}[y]    otherwise,
+// rew being step_multi_body's reward, operation for operation (no contraction: the value of the
+// start cell equals the Horner sum of the rewards its own greedy plan collects, bit for bit).
+// Forward pass: plan_field_kernel's, call for call (a copy: the field's instances keep their
+// registers).  Backward pass: the field's shape -- the env's own rows come back with agent-scope
+// loads one row ahead into two LDS rows, V_{k+1} and V_k are two double [R C] arrays in LDS by
+// tick parity (8-byte aligned, one cell per lane: a wave's 64 doubles are 512 contiguous bytes,
+// read and written as 64-bit LDS accesses with no bank shared inside a half-wave), the five
+// candidates in action order with a strict greater-than (the first maximum wins: a blocked move
+// is a stay and never beats WAIT), one barrier per k.  The tick-independent part of rew is three
+// double operations per candidate and is recomputed; the timeout branch is block-uniform and
+// taken at k = HK - 1 at most.
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_value_kernel(
+    EnvParams p, int H, double gamma, double* __restrict__ value_out, int8_t* __restrict__ action_out,
+    uint32_t* vis_out, double* __restrict__ value_ticks_out, int8_t* __restrict__ action_ticks_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr bool SOLO = W == 1;
+  const int e = block_env(p);
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, N = p.n_envs, C = p.C;
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // cached guard cones of the tick, vis geometry
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6;
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;  // the record's words (obs_record_words)
+  double* val = reinterpret_cast<double*>(uq + 128 * W);           // [2][RC] values, tick parity (16-byte aligned)
+  uint32_t* vrow = reinterpret_cast<uint32_t*>(val + 2 * RC);      // [2][nvis] visibility rows, tick parity
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;
+    prefetch<NT>(p, e, eb, L, raw);
+    if (t < n_slot) rec[t] = raw;
+  }
+  for (int i = t; i < path_words; i += NT) L.path[i] = eb.paths[i];
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  const int g = t - mc;
+  const bool live_cam = t < s.n_cams, live_guard = g >= 0 && g < s.n_guards;
+  bool cached = false;
+  uint4 ca = make_uint4(0u, 0u, 0u, 0u), cb = ca;
+  // a cached guard's cone entry for the coming tick, loaded one tick ahead (step_multi_body)
+  auto next_entry = [&](const Guard& gd) {
+    int idx = gd.idx, slot = gd.hslot;
+    if (gd.len >= 2) {
+      idx += gd.step;
+      if (idx >= gd.len) idx -= gd.len;
+      slot = gd.nslot;
+    }
+    const uint4* src = reinterpret_cast<const uint4*>(eb.cones + cone_off(g, idx, slot));
+    ca = src[0];
+    cb = src[1];
+  };
+  auto take_entry = [&]() {
+    Guard gd = as_guard(rec[t]);
+    gd.nslot = (uint8_t)(cb.w >> 16);  // row 15
+    rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+    uint4* dst = reinterpret_cast<uint4*>(L.cone + 16 * g);
+    dst[0] = ca;
+    dst[1] = cb;
+  };
+  __syncthreads();  // records in LDS
+  if (HK > 0 && live_guard) {
+    const Guard gd = as_guard(rec[t]);
+    cached = gd.hslot != kUncached;
+    if (cached) next_entry(gd);
+  }
+
+  // cell / C as a multiply-shift (plan_kernel)
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+
+  // ---- forward: vis_1 .. vis_HK into the env's rows of vis_out (plan_field_kernel's)
+  for (int k = 1; k <= HK; ++k) {
+    // (the barrier that closed the previous tick's pack also closed its readers of vis / em / cones)
+    Emit E;
+    E.kind = -1;
+    if (w0) {
+      // cameras rotate, guards patrol (security.py:49-51, :145-159), unconditionally
+      if (live_cam) {
+        Cam cm = as_cam(rec[t]);
+        cm.heading = py_mod360(cm.heading + cm.speed * 1.0);
+        rec[t] = __builtin_bit_cast(EmitterRaw, cm);
+        E = cam_emit(cm);
+      } else if (live_guard) {
+        Guard gd = as_guard(rec[t]);
+        const bool moves = gd.len >= 2;
+        int nidx = gd.idx;
+        if (moves) {
+          nidx += gd.step;
+          if (nidx >= gd.len) nidx -= gd.len;
+        }
+        const uint16_t np = moves ? L.path[__umul24((uint32_t)g, (uint32_t)p.max_path) + (uint32_t)nidx] : gd.pos;
+        if (cached) {
+          if (moves) gd.hslot = gd.nslot;
+        } else if (moves) {
+          gd.heading = guard_heading_after(p, unpack_r(np) - unpack_r(gd.pos), unpack_c(np) - unpack_c(gd.pos),
+                                           gd.heading);
+        }
+        gd.idx = (int16_t)nidx;
+        gd.pos = np;
+        rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+        E = guard_emit(gd);
+        if (cached && !SOLO) take_entry();
+      }
+      publish_emitters(L, E, n_slot);
+    }
+    clear_planes<NT>(p, L, gvis, true);
+    __syncthreads();  // emitter table, cone rows, cleared planes
+    if (live_guard && E.kind == 1) L.vis[L.at(E.row, E.col)] = 1;  // visibility.py:59
+    cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+    if (SOLO && cached) take_entry();
+    stamp_guard_cones<NT>(L, gvis, mc, mg, 0);
+    __syncthreads();  // planes complete
+
+    // the tick's plane, 64 cells per ballot, as the two words of its chunk; the pad words are 0
+    uint32_t* row = vis_out + ((size_t)(k - 1) * N + e) * WR;
+    for (int ch = wave; ch < n_chunk; ch += W) {
+      const int cell = 64 * ch + lane;
+      bool on = false;
+      if (cell < RC) {
+        const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+        const int a = L.at(r, c);
+        on = (L.vis[a] | gvis[a]) != 0;
+      }
+      const unsigned long long m = __ballot(on);
+      if (lane < 2 && 2 * ch + lane < WR) row[2 * ch + lane] = (uint32_t)(m >> (32 * lane));
+    }
+    for (int i = 2 * n_chunk + t; i < WR; i += NT) row[i] = 0u;
+    if (w0 && live_guard && cached && k < HK) next_entry(as_guard(rec[t]));  // lands during the next tick
+    __syncthreads();  // the planes' readers are done
+  }
+
+  // the rows this env did not run, 16 bytes per store (WR is a multiple of 4, vis_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - HK) * q4; i += NT) {
+      const int r = HK + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(vis_out + ((size_t)r * N + e) * WR)[q] = z;
+    }
+  }
+  for (int k = HK; k < H; ++k) {
+    const size_t o = ((size_t)k * N + e) * RC;
+    if (value_ticks_out)
+      for (int x = t; x < RC; x += NT) value_ticks_out[o + x] = 0.0;
+    if (action_ticks_out)
+      for (int x = t; x < RC; x += NT) action_ticks_out[o + x] = (int8_t)-1;
+  }
+  if (HK == 0) {  // block-uniform: an env already done (or past max_steps) collects nothing
+    for (int x = t; x < RC; x += NT) {
+      value_out[(size_t)e * RC + x] = 0.0;
+      action_out[(size_t)e * RC + x] = (int8_t)-1;
+    }
+    return;
+  }
+
+  // ---- backward: V_{HK-1} .. V_0
+  __threadfence();  // this env's rows visible to the lanes that read them back
+  for (int x = t; x < RC; x += NT) val[(HK & 1) * RC + x] = 0.0;  // V_HK
+  // row k of vis_out is vis_{k+1}; nvis <= NT for every instance (launch_plan_value checks it)
+  auto load_row = [&](int k) {
+    return __hip_atomic_load(vis_out + ((size_t)k * N + e) * WR + (t < nvis ? t : 0), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  };
+  __syncthreads();
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  const int vr = p.vr, vc = p.vc, vcell = vr * C + vc;
+  const int D0 = uni(s.initial_dist);
+  const bool bonus = D0 > 3;
+  const double r_step = p.r_step, r_detect = p.r_detect, r_vault = p.r_vault;
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;        // vis_{k+1}
+    const double* nxt = val + ((k + 1) & 1) * RC;      // V_{k+1}
+    double* cur = val + (k & 1) * RC;                  // V_k
+    const bool last = tick0 + k + 1 >= p.max_steps;    // the env times out on this tick (k = HK - 1 only)
+    const size_t orow = ((size_t)k * N + e) * RC;
+    for (int x = t; x < RC; x += NT) {
+      double best = 0.0;
+      int act = -1;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        const int dx = iabs_(r - vr) + iabs_(c - vc);
+        // q of the move to cell y = (yr, yc): step_multi_body's reward in its order, then the tail
+        auto q = [&](int y, int yr, int yc) -> double {
+          const int curr = iabs_(yr - vr) + iabs_(yc - vc);
+          double rew = r_step;
+          rew += (double)(dx - curr) * 0.1;
+          if (curr <= 3 && bonus) rew += 0.05 * (double)(3 - curr);
+          const bool seen = ((vk[y >> 5] >> (y & 31)) & 1u) != 0u;
+          if (seen) rew += r_detect;
+          if (y == vcell) rew += r_vault;
+          if (last) {
+            double frac = 1.0 - (double)curr / (double)(D0 > 1 ? D0 : 1);
+            if (frac < 0.0) frac = 0.0;
+            rew += frac * 2.0;
+          }
+          const double on = rew + gamma * nxt[y];
+          return (seen || y == vcell || last) ? rew : on;
+        };
+        best = q(x, r, c);
+        act = 0;
+        bool ok = r > 0 && L.grid[x - C] != kWall;
+        double v = ok ? q(x - C, r - 1, c) : best;
+        if (v > best) best = v, act = 1;
+        ok = r + 1 < p.R && L.grid[x + C] != kWall;
+        v = ok ? q(x + C, r + 1, c) : best;
+        if (v > best) best = v, act = 2;
+        ok = c > 0 && L.grid[x - 1] != kWall;
+        v = ok ? q(x - 1, r, c - 1) : best;
+        if (v > best) best = v, act = 3;
+        ok = c + 1 < C && L.grid[x + 1] != kWall;
+        v = ok ? q(x + 1, r, c + 1) : best;
+        if (v > best) best = v, act = 4;
+      }
+      cur[x] = best;
+      if (value_ticks_out) value_ticks_out[orow + x] = best;
+      if (action_ticks_out) action_ticks_out[orow + x] = (int8_t)act;
+      if (k == 0) {
+        value_out[(size_t)e * RC + x] = best;
+        action_out[(size_t)e * RC + x] = (int8_t)act;
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // V_k and vis_k complete; their previous holders' readers are done
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean K-tick kernel (heist_step_multi, one wave per env, grids up to 20 x 20)
 // ---------------------------------------------------------------------------
 //
@@ -4343,6 +4600,36 @@ hipError_t launch_plan_field(const EnvParams& p, int horizon, int16_t* togo_out,
   }
   HEIST_MULTI_VARIANTS(HEIST_FIELD_CASE)
 #undef HEIST_FIELD_CASE
+  return hipErrorInvalidValue;  // not reached
+}
+
+// heist_plan_value: the field's LDS with two double [R C] arrays in place of the two uint16 ones.
+static size_t plan_value_lds(const EnvParams& p) {
+  const int n_slot = p.max_cams + p.max_guards;
+  return align16(env_lds_bytes(p.R, p.C, n_slot, p.max_guards * p.max_path, p.vis_gap, p.multi_waves, p.max_guards)) +
+         32 * (size_t)n_slot + (size_t)p.vis_gap + align16(sizeof(TieBuckets)) + 1024 * (size_t)p.multi_waves +
+         16 * (size_t)p.RC + 8 * (size_t)((p.RC + 31) >> 5);
+}
+
+// A planner instance, a visibility row that one word per lane fetches, and LDS within the 64 KB a
+// workgroup gets without raising the kernel's dynamic limit (64 x 64: the two value arrays alone
+// are 64 KB -- not supported).
+bool plan_value_variant_exists(const EnvParams& p) {
+  return plan_variant_exists(p) && ((p.RC + 31) >> 5) <= 64 * p.multi_waves && plan_value_lds(p) <= 65536;
+}
+
+hipError_t launch_plan_value(const EnvParams& p, int horizon, double gamma, double* value_out, int8_t* action_out,
+                             uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out, hipStream_t st) {
+  if (!plan_value_variant_exists(p)) return hipErrorInvalidValue;
+  const size_t lds = plan_value_lds(p);
+#define HEIST_VALUE_CASE(W, D)                                                                                   \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                    \
+    hipLaunchKernelGGL((plan_value_kernel<W, D>), dim3(p.n_envs), dim3(64 * W), lds, st, p, horizon, gamma,      \
+                       value_out, action_out, vis_out, value_ticks_out, action_ticks_out);                       \
+    return hipGetLastError();                                                                                    \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_VALUE_CASE)
+#undef HEIST_VALUE_CASE
   return hipErrorInvalidValue;  // not reached
 }
 

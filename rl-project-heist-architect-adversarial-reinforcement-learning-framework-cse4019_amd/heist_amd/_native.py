@@ -37,6 +37,8 @@ SIGNATURES = {
     "heist_plan": (_i, [_vp, _i, _vp, _vp, _vp, _vp]),
     "heist_plan_field_supported": (_i, [_vp]),
     "heist_plan_field": (_i, [_vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "heist_plan_value_supported": (_i, [_vp]),
+    "heist_plan_value": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "heist_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "heist_state_bytes": (_i64, [_vp]),
     "heist_state_save": (_i, [_vp, _vp, _i, _vp, _vp]),

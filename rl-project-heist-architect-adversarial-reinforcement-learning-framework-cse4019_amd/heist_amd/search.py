@@ -7,6 +7,11 @@ the worker envs, action_table builds the launch's actions, select_best picks eac
 follow_field and expert_labels read a planner field (HeistEnv.plan_field(all_ticks=True)): the
 field's own plan from any cell, and the exact ticks to go and optimal action of every state a
 rollout visited.  Both are pure torch and run wherever the field's tensors live.
+
+follow_value, value_targets and discounted_return do the same for a planner value
+(HeistEnv.plan_value(all_ticks=True)): the return-optimal play from any cell, the exact optimal
+return and action of every state a rollout visited, and the return a played rollout collected,
+summed in the value's own order.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -157,6 +162,90 @@ def expert_labels(field, pos_r, pos_c):
         cur, act, _, _ = _field_action(field, k, pr[k], pc[k])
         togo[k], action[k] = cur.to(torch.int16), act.to(torch.int8)
     return togo, action
+
+
+def _need_value_ticks(pv, what, values=False):
+    if pv.action_ticks is None or (values and pv.value_ticks is None):
+        raise ValueError("%s: the value has no per-tick rows (plan_value(all_ticks=True))" % what)
+    if pv.vault is None or pv.grid is None:
+        raise ValueError("%s: the value does not name its vault and grid" % what)
+
+
+def follow_value(pv, pos_r, pos_c):
+    """The return-optimal play from each env's cell (pos_r, pos_c: [N]) as actions [H, N] int64:
+    at step k the Solver takes pv.action_ticks[k] at its cell and moves by pv.grid's walls (a move
+    into a wall or off the grid is a stay).  The rows after the play's terminal step -- the step
+    that ends on a seen cell, on the vault or on the env's last tick -- are 0, as is every row of
+    an env with nothing to play; feed the tensor (or its first rows) to
+    step_multi(auto_reset=False).  Pure torch: runs where pv's tensors live, CPU included."""
+    _need_value_ticks(pv, "follow_value")
+    at, vis = pv.action_ticks, pv.vis
+    H, N, R, C = at.shape
+    dev = at.device
+    n = torch.arange(N, device=dev)
+    r = torch.as_tensor(pos_r, device=dev).long().reshape(N)
+    c = torch.as_tensor(pos_c, device=dev).long().reshape(N)
+    walls = pv.grid.to(dev) == 1
+    vr, vc = pv.vault
+    dr = torch.tensor([d[0] for d in DELTA], device=dev)
+    dc = torch.tensor([d[1] for d in DELTA], device=dev)
+    actions = torch.zeros((H, N), dtype=torch.int64, device=dev)
+    alive = torch.ones(N, dtype=torch.bool, device=dev)
+    for k in range(H):
+        act = at[k, n, r, c].long()
+        alive = alive & (act >= 0)  # -1: past the env's ticks (or a wall cell)
+        if not bool(alive.any()):
+            break
+        a = torch.where(alive, act, torch.zeros_like(act))
+        actions[k] = a
+        yr, yc = r + dr[a], c + dc[a]
+        ok = (yr >= 0) & (yr < R) & (yc >= 0) & (yc < C)
+        yr, yc = yr.clamp(0, R - 1), yc.clamp(0, C - 1)
+        ok = ok & ~walls[n, yr, yc] & alive
+        r, c = torch.where(ok, yr, r), torch.where(ok, yc, c)
+        cell = r * C + c
+        seen = ((vis[k, n, cell >> 5].long() >> (cell & 31)) & 1).bool()
+        alive = alive & ~seen & ~((r == vr) & (c == vc))
+    return actions
+
+
+def value_targets(pv, pos_r, pos_c):
+    """Exact critic targets along a rollout: pos_r, pos_c [K, N] with K <= H, row k the Solver's
+    cell after k ticks (expert_labels' convention).  Returns (value [K, N] float64, action [K, N]
+    int8): pv.value_ticks[k] and pv.action_ticks[k] at that cell -- the optimal return still to
+    collect from that state and the action that starts it.  Pure torch."""
+    _need_value_ticks(pv, "value_targets", values=True)
+    vt, at = pv.value_ticks, pv.action_ticks
+    H, N = vt.shape[:2]
+    dev = vt.device
+    pr, pc = torch.as_tensor(pos_r, device=dev).long(), torch.as_tensor(pos_c, device=dev).long()
+    if pr.dim() != 2 or pr.shape != pc.shape or pr.shape[1] != N or pr.shape[0] > H:
+        raise ValueError("value_targets: cells must be [K, %d] with K <= %d" % (N, H))
+    K = pr.shape[0]
+    k = torch.arange(K, device=dev).reshape(K, 1).expand(K, N)
+    n = torch.arange(N, device=dev).reshape(1, N).expand(K, N)
+    return vt[k, n, pr, pc], at[k, n, pr, pc]
+
+
+def discounted_return(reward64, done, gamma):
+    """[N] float64: per env the Horner sum r_k + gamma * (r_{k+1} + gamma * (...)) of reward64
+    [K, N], started at the env's first tick with done [K, N] set (row K - 1 when there is none)
+    and run backwards to row 0, every operation in float64 and in this order -- the order of
+    heist_plan_value's recurrence, so PlanValue.value at the start cell minus this is a regret
+    that is exactly 0.0 for the play follow_value gives.  Pure torch."""
+    r = torch.as_tensor(reward64).to(torch.float64)
+    d = torch.as_tensor(done, device=r.device).bool()
+    if r.dim() != 2 or r.shape != d.shape:
+        raise ValueError("discounted_return: reward64 and done must both be [K, N]")
+    K, N = r.shape
+    k = torch.arange(K, device=r.device).reshape(K, 1)
+    end = torch.where(d, k, torch.full_like(k, K - 1)).min(dim=0).values  # [N]
+    acc = torch.zeros(N, dtype=torch.float64, device=r.device)
+    g = float(gamma)
+    for i in range(K - 1, -1, -1):
+        tail = g * acc
+        acc = torch.where(i > end, acc, torch.where(i == end, r[i], r[i] + tail))
+    return acc
 
 
 @dataclass

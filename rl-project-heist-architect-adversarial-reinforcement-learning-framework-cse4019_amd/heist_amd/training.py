@@ -159,7 +159,7 @@ class AdversarialTrainer:  # training.py:115-790
                  seed: Optional[int] = None, update_precision: str = "fp32", rollout_precision: str = "fp32",
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
                  solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
-                 track_optimal: bool = False):
+                 track_optimal: bool = False, track_optimal_return: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -204,6 +204,14 @@ class AdversarialTrainer:  # training.py:115-790
         # False: no launch, no metric, logs and checkpoints byte-identical
         self.track_optimal = bool(track_optimal)
         self._optimal = None  # (solvable_frac, optimal_ticks_mean) of the latest planned layout batch
+        # True: every layout batch's optimal return is computed once (HeistEnv.plan_value at gamma
+        # 1, right after its set_layout + reset) and train_iteration reports the latest batch's
+        # optimal_return_mean: the mean over the batch of the largest undiscounted return an
+        # attempt from the start cell can collect.  It is the ceiling of a layout's FIRST attempt
+        # only: a reset keeps the camera headings, so later attempts face another phase of the
+        # cameras.  False: no launch, no metric, logs and checkpoints byte-identical
+        self.track_optimal_return = bool(track_optimal_return)
+        self._optimal_return = None  # optimal_return_mean of the latest valued layout batch
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -337,6 +345,8 @@ class AdversarialTrainer:  # training.py:115-790
                 self.b_scored[mb] = False
                 if self.track_optimal:
                     self._plan_layout_batch(good)
+                if self.track_optimal_return:
+                    self._value_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
@@ -347,6 +357,14 @@ class AdversarialTrainer:  # training.py:115-790
         ok = t > 0
         n_ok, total = (int(x) for x in torch.stack([ok.sum(), (t * ok).sum()]).cpu())
         self._optimal = (n_ok / len(env_ids), total / n_ok if n_ok else float("nan"))
+
+    def _value_layout_batch(self, env_ids):
+        """The optimal undiscounted return, from the start cell, of the layouts just set on env_ids
+        (fresh after reset).  It is the ceiling of the layout's first attempt only: a reset keeps the
+        camera headings, so every later attempt faces another phase of the cameras."""
+        sr, sc = self.config.start_pos
+        v = self.env.plan_value(gamma=1.0).value[torch.as_tensor(env_ids, device=self.device), sr, sc]
+        self._optimal_return = float(v.mean())
 
     # -- rollout / scoring ------------------------------------------------------------------
     @torch.no_grad()
@@ -684,6 +702,8 @@ class AdversarialTrainer:  # training.py:115-790
         out["layouts_scored"] = len(done_ids)
         if self.track_optimal and self._optimal is not None:
             out["solvable_frac"], out["optimal_ticks_mean"] = self._optimal
+        if self.track_optimal_return and self._optimal_return is not None:
+            out["optimal_return_mean"] = self._optimal_return
         return out
 
     # -- public API (training.py:336-416, :606-663) -------------------------------------------

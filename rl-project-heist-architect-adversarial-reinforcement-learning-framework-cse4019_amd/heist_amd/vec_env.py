@@ -149,6 +149,36 @@ class PlanField:
         return bits.reshape(w.shape[0], -1)[:, :self.rows * self.cols].reshape(-1, self.rows, self.cols).bool()
 
 
+@dataclass
+class PlanValue:
+    """HeistEnv.plan_value's output (heist_plan_value, include/heist.h), device tensors:
+    value [N, R, C] float64 -- the largest discounted return (the env's own reward64, summed from
+        the back: r_k + gamma * (...)) a Solver on that cell can still collect as the env stands
+        now; 0.0 on wall cells and in an env already done;
+    action [N, R, C] int8 -- the lowest action that attains it, -1 where there is none to take;
+    vis [H, N, W] int32 -- PlanField.vis: row k - 1 is the visibility plane of the k-th tick from now;
+    value_ticks [H, N, R, C] float64 or None -- row k: the same values k ticks from now (row 0
+        equals value), 0.0 past the env's ticks; with all_ticks=True only.  8 H N R C bytes:
+        2.6 GB for 4,096 envs of 20 x 20 at H = 200;
+    action_ticks [H, N, R, C] int8 or None -- row k: the optimal action of step k, -1 past the
+        env's ticks; with all_ticks=True only;
+    vault -- the vault's (row, col); gamma -- the discount the values were computed with;
+    grid [N, R, C] int8 -- the tile map (export(grid=True)), whose walls
+        heist_amd.search.follow_value moves by."""
+    value: torch.Tensor
+    action: torch.Tensor
+    vis: torch.Tensor
+    value_ticks: Optional[torch.Tensor]
+    action_ticks: Optional[torch.Tensor]
+    rows: int
+    cols: int
+    vault: Optional[Tuple[int, int]] = None
+    gamma: float = 1.0
+    grid: Optional[torch.Tensor] = None
+
+    vis_mask = PlanField.vis_mask
+
+
 class HeistEnv:
     """Batched HeistEnvironment on one HIP device.
 
@@ -423,6 +453,40 @@ class HeistEnv:
             nat.check(nat.lib().heist_plan_field(self._h, H, nat.ptr(togo), nat.ptr(action), nat.ptr(vis), nat.ptr(ticks),
                                                  self._stream()), "heist_plan_field")
         return PlanField(togo, action, vis, ticks, R, C, tuple(int(v) for v in self.config.vault_pos))
+
+    # -- planner value (heist_plan_value) ----------------------------------------------------
+    @property
+    def plan_value_supported(self) -> int:
+        """heist_plan_value_supported: 1 when plan_value() has a kernel for this handle (every
+        grid up to 32 x 32; 0 at 64 x 64, whose value arrays do not fit a workgroup's LDS)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_value_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_value_supported")
+        return d
+
+    def plan_value(self, horizon: Optional[int] = None, gamma: float = 1.0, all_ticks: bool = False) -> "PlanValue":
+        """heist_plan_value: for every env as it stands and every cell, the largest discounted
+        return (the env's own reward64) a Solver on that cell can still collect and the lowest
+        action that starts such a play, plus the visibility plane of every coming tick; with
+        all_ticks the same for every later tick of the horizon (heist_amd.search.follow_value /
+        value_targets read them; value_ticks takes 8 H N R C bytes).  horizon: ticks to look
+        ahead (default config.max_steps, at most 1024); an env runs min(horizon, max_steps - tick),
+        and with fewer than max_steps - tick the return is cut at the horizon.  gamma in [0, 1].
+        Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        kw = dict(device=self.device)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        value = torch.empty((n, R, C), dtype=torch.float64, **kw)
+        action = torch.empty((n, R, C), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, record_words(R, C)), dtype=torch.int32, **kw)
+        vticks = torch.empty((h, n, R, C), dtype=torch.float64, **kw) if all_ticks else None
+        aticks = torch.empty((h, n, R, C), dtype=torch.int8, **kw) if all_ticks else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_value(self._h, H, float(gamma), nat.ptr(value), nat.ptr(action), nat.ptr(vis),
+                                                 nat.ptr(vticks), nat.ptr(aticks), self._stream()), "heist_plan_value")
+        return PlanValue(value, action, vis, vticks, aticks, R, C, tuple(int(v) for v in self.config.vault_pos),
+                         float(gamma), self.export(grid=True)["grid"])
 
     def step_multi_raw(self, K: int, actions: torch.Tensor, obs_out: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, status: torch.Tensor, auto_reset: bool = True) -> None:

@@ -13,6 +13,13 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # heist_plan on the three batches above, one JSON line each,
                                                  # also written to profiles/plan_field.log (--out)
   python tools/plan_env.py --field --all-ticks   # ... and the launch that writes every tick's field as well
+  python tools/plan_env.py --value [--gamma G] [--all-ticks]
+                                                 # the planner value (heist_plan_value, HeistEnv.plan_value) next to
+                                                 # heist_plan_field, same protocol, plus the histogram of the start
+                                                 # cell's value, the share of envs whose return-optimal episode
+                                                 # (follow_value replayed) is longer than plan().ticks and the mean
+                                                 # of value[start] minus the fastest plan's return; also written
+                                                 # to profiles/plan_value.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -107,6 +114,86 @@ def field_table(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def value_table(args, dev):
+    """heist_plan_value next to heist_plan_field, same handle, same process, same state (both only
+    read the envs): one JSON line per batch."""
+    from heist_amd.search import discounted_return, follow_value
+    H = min(args.horizon or args.max_steps, 1024)
+    lines = []
+    for kind in ("architect", "empty", "synthetic"):
+        env = make_env(args, kind, dev)
+        kc = env.kernel_config()
+        assert env.plan_value_supported == 1, kc
+        N = args.envs
+        sr, sc = env.config.start_pos
+        res = env.plan(H)
+        ok = res.ticks > 0
+        # the fastest plan's return and the value's own play, both through the env kernels on a
+        # second handle with the same layouts (the timed handle stays fresh after reset); in chunks,
+        # value_ticks being 8 H N R C bytes
+        twin = make_env(args, kind, dev)
+        _, _, fdone, _, fr64 = twin.step_multi_records(res.actions, auto_reset=False, reward64=True)
+        fast_ret = discounted_return(fr64, fdone, args.gamma)
+        twin.close()
+        v0 = torch.empty(N, dtype=torch.float64, device=dev)
+        ep = torch.empty(N, dtype=torch.int64, device=dev)
+        replay_ok = True
+        step = max(1, min(N, 512))
+        for lo in range(0, N, step):
+            ids = list(range(lo, min(lo + step, N)))
+            part = HeistEnv(len(ids), env.config, max_cams=env.max_cams, max_guards=env.max_guards,
+                            max_path=env.max_path, device=dev, auto_reset=False)
+            assert bool(part.load_state(env.save_state(ids)).all())
+            pv = part.plan_value(H, gamma=args.gamma, all_ticks=True)
+            start_r = torch.full((len(ids),), sr, dtype=torch.int64, device=dev)
+            acts = follow_value(pv, start_r, torch.full_like(start_r, sc))
+            _, _, done, _, r64 = part.step_multi_records(acts, auto_reset=False, reward64=True)
+            v0[lo:lo + len(ids)] = pv.value[:, sr, sc]
+            ep[lo:lo + len(ids)] = done.int().argmax(0) + 1
+            replay_ok &= bool(torch.equal(discounted_return(r64, done, args.gamma).view(torch.int64),
+                                          pv.value[:, sr, sc].contiguous().view(torch.int64)))
+            part.close()
+            del pv
+        hist = {}
+        for v in v0.cpu().tolist():
+            lo = int(v // 2 * 2)
+            hist["%d..%d" % (lo, lo + 2)] = hist.get("%d..%d" % (lo, lo + 2), 0) + 1
+        out = {"config": "%dx%d" % (args.grid, args.grid), "envs": N, "layouts": kind, "horizon": H,
+               "gamma": args.gamma, "multi_waves": kc["multi_waves"], "solvable_frac": float(ok.float().mean()),
+               "replayed_return_equals_value_bitwise": replay_ok,
+               "value_at_start": {"mean": float(v0.mean()), "min": float(v0.min()), "max": float(v0.max()),
+                                  "histogram": dict(sorted(hist.items(), key=lambda kv: float(kv[0].split("..")[0])))},
+               "optimal_episode_ticks_mean": float(ep.float().mean()),
+               "optimal_episode_longer_than_fastest_plan_frac":
+                   float((ep[ok] > res.ticks[ok]).float().mean()) if bool(ok.any()) else None,
+               "optimal_episode_longer_frac_of_all_envs": float(((ep > res.ticks) & ok).float().mean()),
+               "value_minus_fastest_plan_return_mean":
+                   float((v0[ok] - fast_ret[ok]).mean()) if bool(ok.any()) else None}
+        f = statistics.median(timed(dev, lambda: env.plan_field(H), args.warmup, args.runs))
+        ms = timed(dev, lambda: env.plan_value(H, gamma=args.gamma), args.warmup, args.runs)
+        m = statistics.median(ms)
+        out["field_launch_ms_median"] = f
+        out["value"] = {"launch_ms_median": m, "launch_ms": ms, "us_per_tick_of_horizon": m / H * 1e3,
+                        "ns_per_env_tick": m * 1e6 / (H * N), "over_field": m / f, "minus_field_ms": m - f}
+        if args.all_ticks:
+            ms = timed(dev, lambda: env.plan_value(H, gamma=args.gamma, all_ticks=True), args.warmup, args.runs)
+            a = statistics.median(ms)
+            out["value_all_ticks"] = {"launch_ms_median": a, "launch_ms": ms, "over_value": a / m,
+                                      "value_ticks_mb": H * N * args.grid * args.grid * 8 / 1e6,
+                                      "action_ticks_mb": H * N * args.grid * args.grid / 1e6}
+        env.close()
+        lines.append(json.dumps(out))
+        print(lines[-1], flush=True)
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_value.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --value --gamma %r%s\n" % (args.gamma, " --all-ticks" if args.all_ticks else ""))
+        fh.write("\n".join(lines) + "\n")
+
+
+DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--envs", type=int, default=4096)
@@ -120,11 +207,17 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--runs", type=int, default=7)
     ap.add_argument("--field", action="store_true", help="time heist_plan_field next to heist_plan on all three batches")
-    ap.add_argument("--all-ticks", action="store_true", help="with --field: also the launch that writes togo_ticks")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "plan_field.log"), help="--field's log")
+    ap.add_argument("--all-ticks", action="store_true", help="with --field / --value: also the launch that writes "
+                    "togo_ticks / value_ticks and action_ticks")
+    ap.add_argument("--value", action="store_true", help="time heist_plan_value next to heist_plan_field on all three "
+                    "batches, with the start cell's values and the length of the return-optimal episodes")
+    ap.add_argument("--gamma", type=float, default=1.0, help="with --value: the discount")
+    ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.value:
+        return value_table(args, dev)
     if args.field:
         return field_table(args, dev)
     R, N, budget = args.grid, args.envs, args.budget

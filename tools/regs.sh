@@ -1,7 +1,7 @@
 #!/bin/bash
 # Register / occupancy / spill report of the env kernels (cross-compiled for gfx950, no GPU).
 # usage: tools/regs.sh [regex]   (default: step|reset|cones; `plan` the planner's and the planner
-#        field's instances, `field` plan_field_kernel's alone)
+#        field's instances, `field` plan_field_kernel's alone, `value` plan_value_kernel's alone)
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 CSRC=$ROOT/rl-project-heist-architect-adversarial-reinforcement-learning-framework-cse4019_amd/csrc
 OUT=$(mktemp -d)
