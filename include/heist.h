@@ -355,6 +355,54 @@ int heist_plan_value(heist_t h, int horizon, double gamma, double* value_out, in
                      uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out,
                      heist_stream_t stream);
 
+/* Planner playout, no reference counterpart: one episode per env played from a planner's per-tick
+ * tables -- the table's own (expert) play, or that play perturbed on a counter-hashed share of the
+ * steps, every visited state still labelled by the table.  The emitters do not depend on the
+ * Solver, so the play is a function of the visibility rows, the grid, the start cell and the
+ * action rule: no ray is cast and no env is touched.  Env e plays HK = min(horizon, max_steps -
+ * tick[e]) steps, 0 for an env already done; x_0 is pos0[e], or the env's cell when pos0 is NULL.
+ * With move(x, a) as in heist_plan_field, for k = 0 .. HK-1 while the play is live:
+ *   t = action_table[k][e][x_k], the expert's action; an entry outside 0 .. 4 is stored as -1 in
+ *       expert_out and played as WAIT;              value_out[k][e] = value_table[k][e][x_k]
+ *   z = mix64(seed ^ (tick[e] + k) * 0xD1B54A32D192ED03 ^ e * 0x9E3779B97F4A7C15)   (mod 2^64),
+ *       mix64 as under heist_solver_head; the step is noisy iff (z >> 40) < noise_q24 (0: never,
+ *       2^24: always) and then takes a = ((z & 0xFFFFFFFF) * 5) >> 32, else a = t (WAIT for an
+ *       invalid t).  The key holds the env's absolute tick: a call made mid-episode with the same
+ *       seed continues with the same draws.
+ *   y = move(x_k, a);  seen = bit y of vis[k][e];  x_{k+1} = y
+ *   the step's reward is heist_plan_value's rew with x = x_k, line for line, each line one IEEE
+ *       double operation, none contracted, last = tick[e] + k + 1 >= max_steps; it equals the env's
+ *       reward64 of the same actions whenever prev_dist = dist(x_0)
+ *   status = HEIST_RUNNING, then HEIST_DETECTED if seen, then HEIST_VAULT_REACHED if y is the
+ *       vault, then HEIST_TIMEOUT if last (the env's own precedence); done = any of the three
+ *   records_out[k][e] is the compact record of the observation after the step: the visibility
+ *       words are vis[k][e]'s, the position word is y_r | y_c << 8, the padding words are 0
+ * The play ends after a done step; len_out[e] is the number of steps played.  Rows after the end,
+ * and every row of an env with HK = 0, hold action 0, expert -1, value 0.0, a zero record, reward
+ * 0.0, done 1 and status HEIST_ALREADY_DONE; a play the horizon cuts has no such rows.
+ *   action_table [horizon][N][R*C] int8, required: e.g. heist_plan_value's action_ticks_out
+ *   vis          [horizon][N][W] uint32, 16-byte aligned, required: heist_plan_field's /
+ *                heist_plan_value's vis_out of the same handle state
+ *   value_table  [horizon][N][R*C] float64 or NULL, 8-byte aligned: value_ticks_out
+ *   pos0         [N][2] int32 (r, c) or NULL.  A cell outside the grid is found on the device:
+ *                that env plays nothing, all its rows hold the fill and len_out[e] is -1
+ *   actions_out  [horizon][N] int64, required: heist_step_multi's `actions` as it stands
+ *   expert_out   [horizon][N] int8 or NULL;  value_out [horizon][N] float64 or NULL (needs
+ *                value_table);  records_out [horizon][N][W] uint32 or NULL, 16-byte aligned;
+ *                reward64_out [horizon][N] float64 or NULL
+ *   done_out     [horizon][N] uint8 and status_out [horizon][N] int8, required
+ *   len_out      [N] int32 or NULL
+ * The launch only reads the handle (the envs' scalars and grids), as the planners do; every grid
+ * up to 64 x 64 is served (a hand-made table plays where heist_plan_value has no kernel).
+ * HEIST_EINVAL: horizon outside 1..1024, a NULL action_table, vis, actions_out, done_out or
+ * status_out, value_out without value_table, vis or records_out not 16-byte aligned, value_table,
+ * value_out, reward64_out or actions_out not 8-byte aligned, noise_q24 > 2^24. */
+int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const uint32_t* vis,
+                    const double* value_table, const int32_t* pos0, uint32_t noise_q24, uint64_t seed,
+                    int64_t* actions_out, int8_t* expert_out, double* value_out, uint32_t* records_out,
+                    double* reward64_out, uint8_t* done_out, int8_t* status_out, int32_t* len_out,
+                    heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

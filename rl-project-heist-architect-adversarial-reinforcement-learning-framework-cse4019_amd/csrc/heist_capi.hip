@@ -37,6 +37,11 @@ hipError_t launch_plan_field(const EnvParams& p, int horizon, int16_t* togo_out,
 bool plan_value_variant_exists(const EnvParams& p);
 hipError_t launch_plan_value(const EnvParams& p, int horizon, double gamma, double* value_out, int8_t* action_out,
                              uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out, hipStream_t st);
+hipError_t launch_plan_play(const EnvParams& p, int horizon, const int8_t* action_table, const uint32_t* vis,
+                            const double* value_table, const int32_t* pos0, uint32_t noise_q24, uint64_t seed,
+                            int64_t* actions_out, int8_t* expert_out, double* value_out, uint32_t* records_out,
+                            double* reward64_out, uint8_t* done_out, int8_t* status_out, int32_t* len_out,
+                            hipStream_t st);
 hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
                        hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
@@ -622,6 +627,29 @@ int heist_plan_value(heist_t h, int horizon, double gamma, double* value_out, in
   return check_hip(heist::launch_plan_value(q, horizon, gamma, value_out, action_out, vis_out, value_ticks_out,
                                             action_ticks_out, (hipStream_t)stream),
                    "heist_plan_value");
+}
+
+int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const uint32_t* vis, const double* value_table,
+                    const int32_t* pos0, uint32_t noise_q24, uint64_t seed, int64_t* actions_out, int8_t* expert_out,
+                    double* value_out, uint32_t* records_out, double* reward64_out, uint8_t* done_out,
+                    int8_t* status_out, int32_t* len_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_play: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(action_table && vis, "heist_plan_play: null action_table or vis");
+  HEIST_REQUIRE(actions_out && done_out && status_out, "heist_plan_play: null actions_out, done_out or status_out");
+  HEIST_REQUIRE(value_table || !value_out, "heist_plan_play: value_out needs value_table");
+  HEIST_REQUIRE(((uintptr_t)vis & 15) == 0 && ((uintptr_t)records_out & 15) == 0,
+                "heist_plan_play: vis and records_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)value_table & 7) == 0 && ((uintptr_t)value_out & 7) == 0 &&
+                    ((uintptr_t)reward64_out & 7) == 0 && ((uintptr_t)actions_out & 7) == 0,
+                "heist_plan_play: value_table, value_out, reward64_out and actions_out must be 8-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)pos0 & 3) == 0 && ((uintptr_t)len_out & 3) == 0,
+                "heist_plan_play: pos0 / len_out misaligned");
+  HEIST_REQUIRE(noise_q24 <= (1u << 24), "heist_plan_play: need noise_q24 <= 2^24");
+  return check_hip(heist::launch_plan_play(h->p, horizon, action_table, vis, value_table, pos0, noise_q24, seed,
+                                           actions_out, expert_out, value_out, records_out, reward64_out, done_out,
+                                           status_out, len_out, (hipStream_t)stream),
+                   "heist_plan_play");
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

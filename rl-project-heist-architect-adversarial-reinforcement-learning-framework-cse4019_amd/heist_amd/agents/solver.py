@@ -210,6 +210,52 @@ class SolverAgent:  # agents/solver.py:18-259
                     "solver_updates": n_mb * self.ppo_epochs}
         return metrics if defer else metrics()
 
+    def imitation_update(self, obs, expert, value=None, epochs: int = 1, minibatch: Optional[int] = None,
+                         value_coeff: float = 0.5) -> Dict[str, float]:
+        """Supervised steps on exactly labelled states (heist_amd.search.expert_rollout): obs a
+        CompactObs or a [M, 3, R, C] tensor, expert [M] the labelled action (samples with
+        expert < 0 are left out), value [M] the labelled return or None.  The forward is
+        _ppo_epochs' -- zero hidden state, records expanded per minibatch, the fp32 MFMA backbone
+        where it serves the PPO update -- the loss is the mean cross-entropy to expert plus
+        value_coeff times the mean squared error to value, and every step clips the gradient to
+        max_grad_norm and uses the agent's optimizer.  minibatch defaults to batch_size.  Returns
+        imitation_ce, imitation_value_loss and imitation_agreement (the share of samples whose
+        argmax is the expert's action), each the mean over the steps of its value before the
+        step, plus imitation_samples and imitation_updates."""
+        self.network.train()
+        expert = torch.as_tensor(expert, device=self.device).to(torch.int64).reshape(-1)
+        keep = (expert >= 0).nonzero().reshape(-1)
+        n = int(keep.numel())
+        if value is not None:
+            value = torch.as_tensor(value, device=self.device).to(torch.float32).reshape(-1)
+        bs = minibatch or self.batch_size
+        tot = torch.zeros(3, device=self.device)
+        updates = 0
+        params = list(self.network.parameters())
+        for _ in range(epochs if n else 0):
+            perm = keep[torch.randperm(n, device=self.device)]
+            for start in range(0, n, bs):
+                b = perm[start:start + bs]
+                self.optimizer.zero_grad(set_to_none=True)
+                x = obs.expand(b) if isinstance(obs, CompactObs) else obs[b]
+                if x.is_cuda and not (self.update_precision == "fp32" and self.network._train_conv_ok(x)):
+                    x = x.contiguous(memory_format=torch.channels_last)
+                with torch.autocast("cuda", dtype=torch.bfloat16,
+                                    enabled=self.update_precision == "bf16" and x.is_cuda):
+                    logits, new_values, _ = self.network(x)
+                logits, new_values = logits.float(), new_values.float().reshape(-1)
+                ce = F.cross_entropy(logits, expert[b])
+                vloss = F.mse_loss(new_values, value[b]) if value is not None else torch.zeros((), device=self.device)
+                (ce + value_coeff * vloss).backward()
+                agree = (logits.detach().argmax(-1) == expert[b]).float().mean()
+                tot += torch.stack([ce.detach(), vloss.detach(), agree])
+                updates += 1
+                nn.utils.clip_grad_norm_(params, self.max_grad_norm)
+                self.optimizer.step()
+        t = (tot / max(updates, 1)).cpu().numpy()
+        return {"imitation_ce": float(t[0]), "imitation_value_loss": float(t[1]), "imitation_agreement": float(t[2]),
+                "imitation_samples": n, "imitation_updates": updates}
+
     # -- batched API ------------------------------------------------------------------
     @torch.no_grad()
     def act(self, obs: torch.Tensor, hidden=None, generator: Optional[torch.Generator] = None,

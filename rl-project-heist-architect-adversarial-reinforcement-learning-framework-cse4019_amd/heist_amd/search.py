@@ -12,6 +12,11 @@ follow_value, value_targets and discounted_return do the same for a planner valu
 (HeistEnv.plan_value(all_ticks=True)): the return-optimal play from any cell, the exact optimal
 return and action of every state a rollout visited, and the return a played rollout collected,
 summed in the value's own order.
+
+play_table restates heist_plan_play (HeistEnv.plan_play) in pure torch on CPU tensors: one episode
+per env played from per-tick tables, optionally perturbed by counter-hashed uniform actions.
+expert_data / expert_rollout turn such a play into exactly labelled decision states (ExpertData)
+for SolverAgent.imitation_update.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -292,3 +297,191 @@ def exhaustive_lookahead(env, roots: Sequence[int], depth: int, workers: Optiona
     first_reach = torch.where(first <= depth, first, torch.full_like(first, -1))
     best = select_best(returns)
     return LookaheadResult(returns, first_reach, best, _digits(depth).to(dev)[best], wd)
+
+
+# ---- planner playout (heist_plan_play, include/heist.h) in pure torch
+
+_M64 = (1 << 64) - 1
+
+
+def _i64(c: int) -> int:
+    """A 64-bit constant as the int64 with the same bits."""
+    c &= _M64
+    return c - (1 << 64) if c >> 63 else c
+
+
+def _lsr(z: torch.Tensor, s: int) -> torch.Tensor:
+    """Logical right shift of int64 bit patterns."""
+    return (z >> s) & ((1 << (64 - s)) - 1)
+
+
+def _mix64(z: torch.Tensor) -> torch.Tensor:
+    """The header's mix64 (splitmix64 finaliser) on int64 bit patterns; int64 products wrap mod 2^64."""
+    z = z ^ _lsr(z, 30)
+    z = z * _i64(0xBF58476D1CE4E5B9)
+    z = z ^ _lsr(z, 27)
+    z = z * _i64(0x94D049BB133111EB)
+    return z ^ _lsr(z, 31)
+
+
+def play_draws(seed: int, tick: torch.Tensor, env: torch.Tensor) -> torch.Tensor:
+    """heist_plan_play's draw z of (seed, absolute tick, env) as int64 bit patterns, broadcast over
+    tick and env."""
+    key = (tick.to(torch.int64) * _i64(0xD1B54A32D192ED03)) ^ (env.to(torch.int64) * _i64(0x9E3779B97F4A7C15))
+    return _mix64(key ^ _i64(int(seed)))
+
+
+def play_table(table, vis, grid, tick, pos, max_steps, initial_dist, vault, reward_consts=(-0.01, -1.0, 10.0),
+               values=None, done=None, noise=0.0, seed=0, records=True, rewards=True):
+    """heist_plan_play's contract (include/heist.h) in pure torch on CPU tensors, with the handle's
+    share passed in: table [H, N, R, C] int8, vis [H, N, W] int32, grid [N, R, C] int8 (1 = wall),
+    tick [N] and done [N] (None: none done) the envs' ticks and done flags, pos [N, 2] the start
+    cells, max_steps, initial_dist [N], vault (row, col), reward_consts (step, detection, vault),
+    values [H, N, R, C] float64 or None.  Returns a PlanPlay equal to HeistEnv.plan_play's on the
+    same tensors, float64 bit for bit (every reward line is one IEEE double operation)."""
+    from .vec_env import PlanPlay, STATUS_CODES, noise_q24
+    at = torch.as_tensor(table)
+    H, N, R, C = at.shape
+    RC = R * C
+    at = at.reshape(H, N, RC)
+    vis = torch.as_tensor(vis)
+    W, nvis = int(vis.shape[2]), (RC + 31) // 32
+    vt = None if values is None else torch.as_tensor(values).reshape(H, N, RC)
+    walls = torch.as_tensor(grid).reshape(N, R, C) == 1
+    tick = torch.as_tensor(tick).to(torch.int64).reshape(N)
+    D0 = torch.as_tensor(initial_dist).to(torch.int64).reshape(N)
+    pos = torch.as_tensor(pos).to(torch.int64).reshape(N, 2)
+    fin = torch.zeros(N, dtype=torch.bool) if done is None else torch.as_tensor(done).reshape(N) != 0
+    q24 = noise_q24(noise)
+    r_step, r_detect, r_vault = (float(v) for v in reward_consts)
+    vr, vc = int(vault[0]), int(vault[1])
+    n = torch.arange(N)
+    HK = torch.clamp(torch.clamp(int(max_steps) - tick, max=H), min=0)
+    HK = torch.where(fin, torch.zeros_like(HK), HK)
+    r, c = pos[:, 0].clone(), pos[:, 1].clone()
+    off = (r < 0) | (r >= R) | (c < 0) | (c >= C)
+    r, c = r.clamp(0, R - 1), c.clamp(0, C - 1)
+    live = (HK > 0) & ~off
+    out = PlanPlay(torch.zeros((H, N), dtype=torch.int64), torch.full((H, N), -1, dtype=torch.int8),
+                   None if vt is None else torch.zeros((H, N), dtype=torch.float64),
+                   torch.zeros((H, N, W), dtype=torch.int32) if records else None,
+                   torch.zeros((H, N), dtype=torch.float64) if rewards else None,
+                   torch.ones((H, N), dtype=torch.bool),
+                   torch.full((H, N), STATUS_CODES["already_done"], dtype=torch.int8),
+                   torch.zeros(N, dtype=torch.int32))
+    dr = torch.tensor([d[0] for d in DELTA])
+    dc = torch.tensor([d[1] for d in DELTA])
+    denom = torch.clamp(D0, min=1).to(torch.float64)
+    for k in range(H):
+        play = live & (k < HK)
+        if not bool(play.any()):
+            break
+        x = r * C + c
+        t = at[k, n, x].to(torch.int64)
+        ex = torch.where((t < 0) | (t > 4), torch.full_like(t, -1), t)
+        z = play_draws(seed, tick + k, n)
+        noisy = _lsr(z, 40) < q24
+        a = torch.where(noisy, ((z & 0xFFFFFFFF) * 5) >> 32, ex.clamp(min=0))
+        yr, yc = r + dr[a], c + dc[a]
+        ok = (yr >= 0) & (yr < R) & (yc >= 0) & (yc < C)
+        yr, yc = yr.clamp(0, R - 1), yc.clamp(0, C - 1)
+        ok = ok & ~walls[n, yr, yc]
+        yr, yc = torch.where(ok, yr, r), torch.where(ok, yc, c)
+        y = yr * C + yc
+        seen = ((vis[k, n, y >> 5].to(torch.int64) >> (y & 31)) & 1).bool()
+        atv = (yr == vr) & (yc == vc)
+        last = tick + k + 1 >= int(max_steps)
+        dx, curr = (r - vr).abs() + (c - vc).abs(), (yr - vr).abs() + (yc - vc).abs()
+        rew = torch.full((N,), r_step, dtype=torch.float64)
+        rew = rew + (dx - curr).to(torch.float64) * 0.1
+        rew = torch.where((curr <= 3) & (D0 > 3), rew + 0.05 * (3 - curr).to(torch.float64), rew)
+        rew = torch.where(seen, rew + r_detect, rew)
+        rew = torch.where(atv, rew + r_vault, rew)
+        frac = 1.0 - curr.to(torch.float64) / denom
+        frac = torch.where(frac < 0, torch.zeros_like(frac), frac)
+        rew = torch.where(last, rew + frac * 2.0, rew)
+        status = torch.zeros(N, dtype=torch.int8)
+        status[seen] = STATUS_CODES["detected"]
+        status[atv] = STATUS_CODES["vault_reached"]
+        status[last] = STATUS_CODES["timeout"]
+        end = seen | atv | last
+        out.actions[k, play] = a[play]
+        out.expert[k, play] = ex[play].to(torch.int8)
+        if vt is not None:
+            out.value[k, play] = vt[k, n, x][play]
+        if records:
+            rec = vis[k].clone()
+            rec[:, nvis] = (yr | (yc << 8)).to(torch.int32)
+            out.records[k, play] = rec[play]
+        if rewards:
+            out.reward64[k, play] = rew[play]
+        out.done[k, play] = end[play]
+        out.status[k, play] = status[play]
+        out.length += play.to(torch.int32)
+        r, c = torch.where(play, yr, r), torch.where(play, yc, c)
+        live = play & ~end
+    out.length[off] = -1
+    return out
+
+
+@dataclass
+class ExpertData:
+    """Decision states of a table playout, [H, N] time-major: decision k of env e is the state the
+    play's step k was taken from, valid iff k < length[e].
+    records [H, N, W] int32 -- decision k's observation record (decision 0: the caller's, decision
+        k >= 1: the play's record k - 1);
+    expert [H, N] int8 -- the table's action there (-1: none), value [H, N] float64 or None -- the
+        table's value there, taken [H, N] int64 -- the action the play took;
+    valid [H, N] bool, length [N] int32; grid [N, R, C] int8 -- the tile map the records expand by."""
+    records: torch.Tensor
+    expert: torch.Tensor
+    value: Optional[torch.Tensor]
+    taken: torch.Tensor
+    valid: torch.Tensor
+    length: torch.Tensor
+    grid: torch.Tensor
+    rows: int
+    cols: int
+    vault: tuple
+
+    def flat(self, mask=None):
+        """The valid decisions (of the envs mask [N] bool selects; None: all) as (CompactObs, expert
+        int64, value float32 or None, taken int64), env-minor in tick order."""
+        from .obs_compact import CompactObs
+        H, N = self.valid.shape
+        keep = self.valid
+        if mask is not None:
+            keep = keep & torch.as_tensor(mask, device=keep.device).bool().reshape(1, N)
+        idx = keep.reshape(-1).nonzero().reshape(-1)
+        env = torch.arange(N, dtype=torch.int32, device=idx.device).repeat(H)[idx]
+        obs = CompactObs(self.records.reshape(H * N, -1)[idx], env, self.grid, self.rows, self.cols, self.vault)
+        value = None if self.value is None else self.value.reshape(-1)[idx].to(torch.float32)
+        return obs, self.expert.reshape(-1)[idx].to(torch.int64), value, self.taken.reshape(-1)[idx]
+
+
+def expert_data(play, records0, grid, rows, cols, vault) -> ExpertData:
+    """The decision states of a PlanPlay that kept its records: records0 [N, W] int32 is the record
+    of the observation the first action was chosen from.  Pure torch."""
+    if play.records is None:
+        raise ValueError("expert_data: the play has no records (plan_play(records=True))")
+    H, N = play.actions.shape
+    rec = torch.cat([torch.as_tensor(records0, device=play.records.device).reshape(1, N, -1), play.records[:H - 1]], 0)
+    k = torch.arange(H, device=play.length.device).reshape(H, 1)
+    valid = k < play.length.reshape(1, N).to(torch.int64)
+    return ExpertData(rec, play.expert, play.value, play.actions, valid, play.length, torch.as_tensor(grid),
+                      int(rows), int(cols), (int(vault[0]), int(vault[1])))
+
+
+def expert_rollout(env, gamma: float = 1.0, horizon: Optional[int] = None, noise: float = 0.0, seed: int = 0,
+                   records0: Optional[torch.Tensor] = None) -> ExpertData:
+    """Exactly labelled decision states of every env of a HeistEnv as it stands: one
+    plan_value(all_ticks=True) launch and one plan_play launch of its tables, the play perturbed
+    with probability noise per step (states off the optimal path, still labelled by the exact
+    table).  records0 [N, W] is the record of each env's current observation; it defaults to
+    env.pack_obs(env.obs), so env.obs must be current -- it is after reset or step, not after
+    step_multi, load_state or fork_state.  Reads the envs only."""
+    pv = env.plan_value(horizon=horizon, gamma=gamma, all_ticks=True)
+    play = env.plan_play(pv.action_ticks, pv.vis, values=pv.value_ticks, noise=noise, seed=seed)
+    if records0 is None:
+        records0 = env.pack_obs(env.obs)
+    return expert_data(play, records0, pv.grid, env.rows, env.cols, env.config.vault_pos)

@@ -706,6 +706,64 @@ class AdversarialTrainer:  # training.py:115-790
             out["optimal_return_mean"] = self._optimal_return
         return out
 
+    # -- supervised pre-training on exact labels (no reference counterpart) -------------------
+    def pretrain_solver(self, iterations: int, n_envs: Optional[int] = None, noise: float = 0.1, seed: int = 0,
+                        layouts="architect") -> List[Dict[str, float]]:
+        """Imitation steps of the Solver on the planner's exact labels: each iteration sets fresh
+        layouts on a HeistEnv handle of its own, resets it, plays every BFS-valid env from its
+        value tables with probability noise of a uniform action per step (search.expert_rollout:
+        states off the optimal path too, each labelled with the optimal action and return) and
+        runs one SolverAgent.imitation_update on the decision states.  layouts: "architect"
+        (the Architect's samples at the current curriculum phase and temperature, not recorded),
+        "empty", or a LayoutBatch sized for n_envs.  n_envs defaults to the trainer's, cut so that
+        the value table (8 H N R C bytes) stays under 1 GB.  The trainer's env batch and
+        bookkeeping, global_episode, the logs and the Architect (network, buffers, budget) are
+        left as they were; only the Solver's network and optimizer change.  Returns the metrics
+        of every iteration.  Single-process only: imitation_update does not average gradients
+        across ranks."""
+        from .search import expert_rollout
+        from .vec_env import LayoutBatch
+        if dist_utils.is_multi():
+            raise RuntimeError("pretrain_solver: not collective; pre-train on one rank and broadcast the weights")
+        cfg = self.config
+        R, C, H = cfg.grid_rows, cfg.grid_cols, min(int(cfg.max_steps), 1024)
+        if n_envs is None:
+            n_envs = max(1, min(self.n_envs, 10 ** 9 // (8 * H * R * C)))
+        pe = getattr(self, "_pretrain_env", None)
+        if pe is None or pe.n_envs != n_envs:
+            if pe is not None:
+                pe.close()
+            pe = HeistEnv(n_envs, cfg, max_cams=self.env.max_cams, max_guards=self.env.max_guards,
+                          max_path=self.env.max_path, device=self.device, auto_reset=False)
+            self._pretrain_env = pe
+        out = []
+        for it in range(iterations):
+            if isinstance(layouts, LayoutBatch):
+                valid = pe.set_layout_batch(layouts)
+            elif layouts == "empty":
+                valid = pe.set_layouts([([], [], [])] * n_envs, budget=cfg.architect_budget)
+            elif layouts == "architect":
+                ep = self.global_episode + 1
+                _, budget, cams, guards, _ = self.get_curriculum_phase(ep)
+                saved = self.architect.budget
+                self.architect.budget = budget
+                try:
+                    lb, _, _ = self.architect.generate_layouts(n_envs, self._temperature(ep), cams, guards, env=pe,
+                                                               record=False)
+                finally:
+                    self.architect.budget = saved
+                valid = pe.set_layout_batch(lb)
+            else:
+                raise ValueError("pretrain_solver: layouts must be 'architect', 'empty' or a LayoutBatch")
+            valid = valid.bool()
+            pe.reset()
+            data = expert_rollout(pe, gamma=self.solver.gamma, noise=noise, seed=seed + it)
+            obs, expert, value, _ = data.flat(valid)
+            m = self.solver.imitation_update(obs, expert, value, minibatch=self.minibatch)
+            m["pretrain_valid_envs"] = int(valid.sum())
+            out.append(m)
+        return out
+
     # -- public API (training.py:336-416, :606-663) -------------------------------------------
     def _run_warmup(self, rollouts: int = 2):
         """Warmup on empty layouts (training.py:277-330)."""

@@ -179,6 +179,38 @@ class PlanValue:
     vis_mask = PlanField.vis_mask
 
 
+@dataclass
+class PlanPlay:
+    """HeistEnv.plan_play's output (heist_plan_play, include/heist.h; heist_amd.search.play_table
+    gives the same on CPU tensors): one episode per env played from a planner's per-tick tables.
+    actions [H, N] int64 -- the actions taken, heist_step_multi's `actions` as it stands;
+    expert [H, N] int8 -- the table's action in the state the step was taken from, -1 where the
+        table has none (played as WAIT);
+    value [H, N] float64 or None -- the value table's entry in that state;
+    records [H, N, W] int32 or None -- the compact record of the observation after the step;
+    reward64 [H, N] float64 or None -- the step's reward, the env's own reward64 bit for bit;
+    done [H, N] bool, status [H, N] int8 -- the env's own (STATUS_NAMES);
+    length [N] int32 -- the steps played, -1 for a start cell outside the grid.
+    Rows after a play's end hold action 0, expert -1, value 0.0, a zero record, reward 0.0, done
+    True and status already_done."""
+    actions: torch.Tensor
+    expert: torch.Tensor
+    value: Optional[torch.Tensor]
+    records: Optional[torch.Tensor]
+    reward64: Optional[torch.Tensor]
+    done: torch.Tensor
+    status: torch.Tensor
+    length: torch.Tensor
+
+
+def noise_q24(noise: float) -> int:
+    """A noise probability in [0, 1] as heist_plan_play's 24-bit threshold, round(noise * 2^24)."""
+    q = int(round(float(noise) * (1 << 24)))
+    if not 0 <= q <= 1 << 24:
+        raise ValueError("noise must be in [0, 1], got %r" % (noise,))
+    return q
+
+
 class HeistEnv:
     """Batched HeistEnvironment on one HIP device.
 
@@ -487,6 +519,54 @@ class HeistEnv:
                                                  nat.ptr(vticks), nat.ptr(aticks), self._stream()), "heist_plan_value")
         return PlanValue(value, action, vis, vticks, aticks, R, C, tuple(int(v) for v in self.config.vault_pos),
                          float(gamma), self.export(grid=True)["grid"])
+
+    # -- planner playout (heist_plan_play) ---------------------------------------------------
+    def plan_play(self, table: torch.Tensor, vis: torch.Tensor, values: Optional[torch.Tensor] = None,
+                  pos: Optional[torch.Tensor] = None, noise: float = 0.0, seed: int = 0, records: bool = True,
+                  rewards: bool = True) -> "PlanPlay":
+        """heist_plan_play: one episode per env played from per-tick tables in one launch that
+        casts no ray and touches no env.  table [H, N, R, C] int8 (plan_value(all_ticks=True)'s
+        action_ticks, or any table of actions per tick and cell), vis [H, N, W] int32 (the same
+        plan's vis), values [H, N, R, C] float64 or None (value_ticks), pos [N, 2] (row, col) start
+        cells or None for the envs' own.  With probability noise (rounded to 24 bits) a step
+        takes a uniform action instead of the table's, drawn from a hash of (seed, the env's
+        tick, the env): the same seed continues the same draws mid-episode.  records / rewards:
+        also return every step's compact record / float64 reward.  Reads the envs only."""
+        from .obs_compact import record_words
+        n, R, C = self.n_envs, self.rows, self.cols
+        W = record_words(R, C)
+        H = int(table.shape[0]) if table.dim() else 0
+        dev = self.device
+
+        def arg(t, dtype, shape, what, align=1):
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError("plan_play: %s must be a %s %s tensor" % (what, dtype, shape))
+            if t.device != dev or not t.is_contiguous() or t.data_ptr() % align:
+                t = t.to(dev).contiguous()
+                if t.data_ptr() % align:
+                    t = t.clone()
+            return t
+        table = arg(table, torch.int8, (H, n, R, C), "table")
+        vis = arg(vis, torch.int32, (H, n, W), "vis", 16)
+        if values is not None:
+            values = arg(values, torch.float64, (H, n, R, C), "values", 8)
+        if pos is not None:
+            pos = torch.as_tensor(pos).to(device=dev, dtype=torch.int32).reshape(n, 2).contiguous()
+        kw = dict(device=dev)
+        out = PlanPlay(torch.empty((H, n), dtype=torch.int64, **kw), torch.empty((H, n), dtype=torch.int8, **kw),
+                       None if values is None else torch.empty((H, n), dtype=torch.float64, **kw),
+                       torch.empty((H, n, W), dtype=torch.int32, **kw) if records else None,
+                       torch.empty((H, n), dtype=torch.float64, **kw) if rewards else None,
+                       torch.empty((H, n), dtype=torch.uint8, **kw), torch.empty((H, n), dtype=torch.int8, **kw),
+                       torch.empty(n, dtype=torch.int32, **kw))
+        P = nat.ptr
+        with torch.cuda.device(dev):
+            nat.check(nat.lib().heist_plan_play(self._h, H, P(table), P(vis), P(values), P(pos), noise_q24(noise),
+                                                int(seed) & (2 ** 64 - 1), P(out.actions), P(out.expert), P(out.value),
+                                                P(out.records), P(out.reward64), P(out.done), P(out.status),
+                                                P(out.length), self._stream()), "heist_plan_play")
+        out.done = out.done.view(torch.bool)
+        return out
 
     def step_multi_raw(self, K: int, actions: torch.Tensor, obs_out: torch.Tensor, reward: torch.Tensor,
                        done: torch.Tensor, status: torch.Tensor, auto_reset: bool = True) -> None:

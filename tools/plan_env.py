@@ -20,6 +20,12 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # (follow_value replayed) is longer than plan().ticks and the mean
                                                  # of value[start] minus the fastest plan's return; also written
                                                  # to profiles/plan_value.log
+  python tools/plan_env.py --play [--noise P] [--gamma G]
+                                                 # the planner playout (heist_plan_play, HeistEnv.plan_play) on the
+                                                 # Architect batch: with and without records, at noise 0 and P, next
+                                                 # to the path it replaces (follow_value + step_multi_records on a
+                                                 # twin handle restored from the saved state + value_targets) and to
+                                                 # heist_plan_value itself; also written to profiles/plan_play.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -191,6 +197,77 @@ def value_table(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def play_table_mode(args, dev):
+    """heist_plan_play next to the Python path it replaces and to heist_plan_value, same process,
+    same handle (all of them only read it; the replay runs on a twin restored from its state)."""
+    from heist_amd.search import follow_value, value_targets
+    H = min(args.horizon or args.max_steps, 1024)
+    N, R = args.envs, args.grid
+    env = make_env(args, args.layouts, dev)
+    kc = env.kernel_config()
+    assert env.plan_value_supported == 1, kc
+    sr, sc = env.config.start_pos
+    nvis = (R * R + 31) // 32
+    pv = env.plan_value(H, gamma=args.gamma, all_ticks=True)
+    state = env.save_state()
+    twin = HeistEnv(N, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                    auto_reset=False)
+    start_r = torch.full((N,), sr, dtype=torch.int64, device=dev)
+    start_c = torch.full_like(start_r, sc)
+
+    def python_path():
+        acts = follow_value(pv, start_r, start_c)
+        twin.load_state(state)
+        rec, _, done, status, r64 = twin.step_multi_records(acts, auto_reset=False, reward64=True)
+        word = rec[:, :, nvis].long()
+        pos_r = torch.cat([start_r[None], (word & 0xFF)[:-1]])
+        pos_c = torch.cat([start_c[None], ((word >> 8) & 0xFF)[:-1]])
+        return acts, rec, r64, done, status, value_targets(pv, pos_r, pos_c)
+
+    out = {"config": "%dx%d" % (R, R), "envs": N, "layouts": args.layouts, "horizon": H, "gamma": args.gamma,
+           "multi_waves": kc["multi_waves"], "noise": args.noise}
+    ref = python_path()
+    p0 = env.plan_play(pv.action_ticks, pv.vis, values=pv.value_ticks, noise=0.0, seed=args.seed)
+    played = torch.arange(H, device=dev).reshape(H, 1) < p0.length.reshape(1, N)
+    out["noise0_equals_python_path"] = bool(
+        torch.equal(p0.actions, ref[0]) and torch.equal(p0.records[played], ref[1][played])
+        and torch.equal(p0.reward64.view(torch.int64), ref[2].view(torch.int64)) and torch.equal(p0.done, ref[3])
+        and torch.equal(p0.status, ref[4]) and torch.equal(p0.value[played].view(torch.int64),
+                                                          ref[5][0][played].view(torch.int64)))
+    pn = env.plan_play(pv.action_ticks, pv.vis, values=pv.value_ticks, noise=args.noise, seed=args.seed)
+    for name, p in (("noise0", p0), ("noisy", pn)):
+        last = p.status.gather(0, (p.length.long() - 1).clamp(min=0).reshape(1, N))[0]
+        out[name] = {"length_mean": float(p.length.float().mean()),
+                     "ended": {k: float((last == v).float().mean())
+                               for k, v in (("detected", 1), ("vault_reached", 2), ("timeout", 3))},
+                     "steps_off_expert_frac": float(((p.actions != p.expert.long()) & (p.expert >= 0)).sum())
+                     / max(1.0, float(p.length.clamp(min=0).sum()))}
+    for records in (True, False):
+        for noise in (0.0, args.noise):
+            ms = timed(dev, lambda: env.plan_play(pv.action_ticks, pv.vis, values=pv.value_ticks, noise=noise,
+                                                  seed=args.seed, records=records), args.warmup, args.runs)
+            out["play_%s_noise_%g" % ("records" if records else "no_records", noise)] = {
+                "launch_ms_median": statistics.median(ms), "launch_ms": ms}
+    ms = timed(dev, python_path, args.warmup, args.runs)
+    out["python_path"] = {"ms_median": statistics.median(ms), "ms": ms}
+    for all_ticks in (False, True):
+        ms = timed(dev, lambda: env.plan_value(H, gamma=args.gamma, all_ticks=all_ticks), args.warmup, args.runs)
+        out["plan_value_all_ticks" if all_ticks else "plan_value"] = {"launch_ms_median": statistics.median(ms),
+                                                                      "launch_ms": ms}
+    m = out["play_records_noise_0"]["launch_ms_median"]
+    out["python_path_over_play"] = out["python_path"]["ms_median"] / m
+    out["play_over_plan_value_all_ticks"] = m / out["plan_value_all_ticks"]["launch_ms_median"]
+    env.close()
+    twin.close()
+    line = json.dumps(out)
+    print(line, flush=True)
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_play.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --play --noise %r --gamma %r\n" % (args.noise, args.gamma))
+        fh.write(line + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -212,10 +289,16 @@ def main(argv=None):
     ap.add_argument("--value", action="store_true", help="time heist_plan_value next to heist_plan_field on all three "
                     "batches, with the start cell's values and the length of the return-optimal episodes")
     ap.add_argument("--gamma", type=float, default=1.0, help="with --value: the discount")
-    ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log)")
+    ap.add_argument("--play", action="store_true", help="time heist_plan_play next to the Python path it replaces and "
+                    "to heist_plan_value on the --layouts batch")
+    ap.add_argument("--noise", type=float, default=0.1, help="with --play: the noisy configurations' probability")
+    ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
+                    "profiles/plan_play.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.play:
+        return play_table_mode(args, dev)
     if args.value:
         return value_table(args, dev)
     if args.field:
