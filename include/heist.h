@@ -403,6 +403,48 @@ int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const ui
                     double* reward64_out, uint8_t* done_out, int8_t* status_out, int32_t* len_out,
                     heist_stream_t stream);
 
+/* Planner Q, no reference counterpart: the five exact action values of every visited state -- the
+ * one-step lookahead heist_plan_value's recurrence defines, on caller-chosen states instead of
+ * every cell -- with their maximum, the set of optimal actions and the loss of the action taken.
+ * t0[e] is tick0[e], or with tick0 NULL the env's tick now (-1 for an env that is done now): the
+ * env's tick when the tables were made, -1 for an env that was done then, which lets a rollout be
+ * labelled after the handle has been stepped through it.  Env e has HK = min(horizon, max_steps -
+ * t0[e]) steps, 0 for t0[e] < 0.  A state is (k, e, x = pos[k][e]), the cell the Solver stands on
+ * k ticks after t0 (row 0 the cell then: heist_amd.search.expert_labels' convention); it is live
+ * when k < HK, x is inside the grid and x is not a wall cell.  For a live state and a = 0 .. 4 in
+ * order, with y = move(x, a) as in heist_plan_field,
+ *   q[a] = heist_plan_value's q of (x, a, k), line for line, each line one IEEE double operation,
+ *          none contracted: rew (its six lines), seen = bit y of vis[k][e], last = t0[e] + k + 1 >=
+ *          max_steps, q = (seen or y == vault or last) ? rew : rew + gamma * V_{k+1}[y], where
+ *          V_{k+1}[y] is value_table[k+1][e][y] when k + 1 < horizon, else 0.0
+ *   value = the maximum q under a strict greater-than, best = its first a: for tables made by
+ *          heist_plan_value with the same gamma on the same handle state they equal
+ *          value_ticks_out[k][e][x] and action_ticks_out[k][e][x] bit for bit
+ *   optimal: bit a is set iff q[a] == value (exact double equality; a blocked move that ties with
+ *          an optimal WAIT is in the set: it is the same transition)
+ *   gap = value - q[taken[k][e]], one subtraction; an entry of taken outside 0 .. 4 counts as WAIT,
+ *          as in heist_plan_play.  gap is exactly 0.0 iff the taken action is in the optimal set.
+ * A state that is not live holds q = 0.0 five times, value 0.0, best -1, optimal 0 and gap 0.0.
+ *   value_table [horizon][N][R*C] float64, 8-byte aligned, required: e.g. value_ticks_out
+ *   vis         [horizon][N][W] uint32, 16-byte aligned, required: heist_plan_value's /
+ *               heist_plan_field's vis_out (row k holds vis_{k+1})
+ *   tick0       [N] int32 or NULL;  pos [K][N][2] int32 (r, c), 1 <= K <= horizon, required
+ *   taken       [K][N] int64 or NULL
+ *   q_out [K][N][5] float64, value_out [K][N] float64, best_out [K][N] int8, optimal_out [K][N]
+ *               uint8, gap_out [K][N] float64 (needs taken): each may be NULL, not all of them
+ * From the handle the launch reads only what does not change within an episode -- the grid, the
+ * vault, initial_dist, max_steps and reward_consts (and, with tick0 NULL, tick and done) -- so the
+ * handle's layout must be the one the tables were made for; it writes the caller's arrays alone.
+ * Every grid up to 64 x 64 is served (no LDS array per cell: a hand-made table is labelled where
+ * heist_plan_value has no kernel).
+ * HEIST_EINVAL: horizon outside 1..1024, K outside 1..horizon, gamma not finite or outside [0, 1],
+ * a NULL value_table, vis or pos, every output NULL, gap_out without taken, vis not 16-byte
+ * aligned, value_table, taken, q_out, value_out or gap_out not 8-byte aligned, tick0 or pos not
+ * 4-byte aligned, a probe mode armed (HEIST_PROBE_MODE). */
+int heist_plan_q(heist_t h, int horizon, int K, double gamma, const double* value_table, const uint32_t* vis,
+                 const int32_t* tick0, const int32_t* pos, const int64_t* taken, double* q_out, double* value_out,
+                 int8_t* best_out, uint8_t* optimal_out, double* gap_out, heist_stream_t stream);
+
 /* Instrumentation, no reference counterpart: with counter a device array of n_envs uint64,
  * every later heist_step / heist_reset on h adds to counter[e] the number of ray samples
  * env e evaluated (the ALU work figure of SURVEY 8(d)); NULL switches counting off (default). */

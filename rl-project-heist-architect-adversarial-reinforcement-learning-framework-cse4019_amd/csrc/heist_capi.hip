@@ -42,6 +42,10 @@ hipError_t launch_plan_play(const EnvParams& p, int horizon, const int8_t* actio
                             int64_t* actions_out, int8_t* expert_out, double* value_out, uint32_t* records_out,
                             double* reward64_out, uint8_t* done_out, int8_t* status_out, int32_t* len_out,
                             hipStream_t st);
+hipError_t launch_plan_q(const EnvParams& p, int horizon, int K, double gamma, const double* value_table,
+                         const uint32_t* vis, const int32_t* tick0, const int32_t* pos, const int64_t* taken,
+                         double* q_out, double* value_out, int8_t* best_out, uint8_t* optimal_out, double* gap_out,
+                         hipStream_t st);
 hipError_t launch_plan(const EnvParams& p, int horizon, int32_t* ticks_out, int64_t* actions_out, uint32_t* reach_out,
                        hipStream_t st);
 hipError_t launch_bfs(const int32_t* grid, int n, int R, int C, int sr, int sc, int gr, int gc, uint8_t* out,
@@ -650,6 +654,27 @@ int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const ui
                                            actions_out, expert_out, value_out, records_out, reward64_out, done_out,
                                            status_out, len_out, (hipStream_t)stream),
                    "heist_plan_play");
+}
+
+int heist_plan_q(heist_t h, int horizon, int K, double gamma, const double* value_table, const uint32_t* vis,
+                 const int32_t* tick0, const int32_t* pos, const int64_t* taken, double* q_out, double* value_out,
+                 int8_t* best_out, uint8_t* optimal_out, double* gap_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_q: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(K >= 1 && K <= horizon, "heist_plan_q: need 1 <= K <= horizon");
+  HEIST_REQUIRE(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "heist_plan_q: need 0 <= gamma <= 1");
+  HEIST_REQUIRE(value_table && vis && pos, "heist_plan_q: null value_table, vis or pos");
+  HEIST_REQUIRE(q_out || value_out || best_out || optimal_out || gap_out, "heist_plan_q: every output is null");
+  HEIST_REQUIRE(taken || !gap_out, "heist_plan_q: gap_out needs taken");
+  HEIST_REQUIRE(((uintptr_t)vis & 15) == 0, "heist_plan_q: vis must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)value_table & 7) == 0 && ((uintptr_t)taken & 7) == 0 && ((uintptr_t)q_out & 7) == 0 &&
+                    ((uintptr_t)value_out & 7) == 0 && ((uintptr_t)gap_out & 7) == 0,
+                "heist_plan_q: value_table, taken, q_out, value_out and gap_out must be 8-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)tick0 & 3) == 0 && ((uintptr_t)pos & 3) == 0, "heist_plan_q: tick0 / pos misaligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan_q: a probe mode is armed (HEIST_PROBE_MODE)");
+  return check_hip(heist::launch_plan_q(h->p, horizon, K, gamma, value_table, vis, tick0, pos, taken, q_out, value_out,
+                                        best_out, optimal_out, gap_out, (hipStream_t)stream),
+                   "heist_plan_q");
 }
 
 int heist_export(heist_t h, int32_t* scalars, int8_t* grid, double* cam_heading, int32_t* guard_idx,

@@ -7,8 +7,8 @@ hand-written HIP kernels for gfx950 behind the C ABI in include/heist.h
 __version__ = "0.1.0"
 
 from .environment import EnvironmentConfig, HeistEnvironment  # noqa: F401
-from .vec_env import HeistEnv, LayoutBatch, PlanField, PlanPlay, PlanResult, PlanValue, STATUS_NAMES  # noqa: F401
-from .obs_compact import CompactObs  # noqa: F401
+from .vec_env import HeistEnv, LayoutBatch, PlanField, PlanPlay, PlanQ, PlanResult, PlanValue, STATUS_NAMES  # noqa: F401
+from .obs_compact import CompactObs, record_cells  # noqa: F401
 from .env_state import EnvState  # noqa: F401
 from .search import (ExpertData, LookaheadResult, exhaustive_lookahead, expert_data, expert_labels,  # noqa: F401
-                     expert_rollout, follow_field, play_table)
+                     expert_rollout, follow_field, play_table, q_values)

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("HEIST_LIB") or os.path.join(os.path.dirname(os.path.a
 BUILD_DIR = os.path.join(PKG_ROOT, "build")
 ARCH = os.environ.get("HEIST_OFFLOAD_ARCH", "gfx950")
 SOURCES = ["heist_env.hip", "heist_arch.hip", "heist_arch_update.hip", "heist_ppo.hip", "heist_policy.hip", "heist_train.hip",
-           "heist_train_conv.hip", "heist_obs.hip", "heist_state.hip", "heist_play.hip", "heist_capi.hip"]
+           "heist_train_conv.hip", "heist_obs.hip", "heist_state.hip", "heist_play.hip", "heist_q.hip", "heist_capi.hip"]
 # headers are found per source by following its #include "..." lines (_includes)
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # heist_env.hip: no SLP vectorization -- ROCm 7.2 clang miscompiles the packed-fp32

@@ -211,7 +211,7 @@ class SolverAgent:  # agents/solver.py:18-259
         return metrics if defer else metrics()
 
     def imitation_update(self, obs, expert, value=None, epochs: int = 1, minibatch: Optional[int] = None,
-                         value_coeff: float = 0.5) -> Dict[str, float]:
+                         value_coeff: float = 0.5, optimal=None) -> Dict[str, float]:
         """Supervised steps on exactly labelled states (heist_amd.search.expert_rollout): obs a
         CompactObs or a [M, 3, R, C] tensor, expert [M] the labelled action (samples with
         expert < 0 are left out), value [M] the labelled return or None.  The forward is
@@ -221,10 +221,21 @@ class SolverAgent:  # agents/solver.py:18-259
         max_grad_norm and uses the agent's optimizer.  minibatch defaults to batch_size.  Returns
         imitation_ce, imitation_value_loss and imitation_agreement (the share of samples whose
         argmax is the expert's action), each the mean over the steps of its value before the
-        step, plus imitation_samples and imitation_updates."""
+        step, plus imitation_samples and imitation_updates.
+        optimal [M]: the set of optimal actions of each sample as a bit mask (bit a = action a,
+        PlanQ.optimal).  With it the labels are sets: the policy loss is -log of the probability
+        the policy gives the set (logsumexp of all logits minus logsumexp over the set's),
+        imitation_ce reports it, imitation_agreement counts an argmax inside the set, samples
+        with an empty set are left out and expert is not read (it may be None)."""
         self.network.train()
-        expert = torch.as_tensor(expert, device=self.device).to(torch.int64).reshape(-1)
-        keep = (expert >= 0).nonzero().reshape(-1)
+        sets = None
+        if optimal is not None:
+            bits = torch.as_tensor(optimal, device=self.device).to(torch.int64).reshape(-1, 1)
+            sets = ((bits >> torch.arange(self.num_actions, device=self.device)) & 1).bool()  # [M, A]
+            keep = sets.any(1).nonzero().reshape(-1)
+        else:
+            expert = torch.as_tensor(expert, device=self.device).to(torch.int64).reshape(-1)
+            keep = (expert >= 0).nonzero().reshape(-1)
         n = int(keep.numel())
         if value is not None:
             value = torch.as_tensor(value, device=self.device).to(torch.float32).reshape(-1)
@@ -244,10 +255,16 @@ class SolverAgent:  # agents/solver.py:18-259
                                     enabled=self.update_precision == "bf16" and x.is_cuda):
                     logits, new_values, _ = self.network(x)
                 logits, new_values = logits.float(), new_values.float().reshape(-1)
-                ce = F.cross_entropy(logits, expert[b])
+                if sets is None:
+                    ce = F.cross_entropy(logits, expert[b])
+                    agree = (logits.detach().argmax(-1) == expert[b]).float().mean()
+                else:
+                    inset = sets[b]
+                    ce = (torch.logsumexp(logits, -1)
+                          - torch.logsumexp(logits.masked_fill(~inset, float("-inf")), -1)).mean()
+                    agree = inset.gather(1, logits.detach().argmax(-1, keepdim=True)).float().mean()
                 vloss = F.mse_loss(new_values, value[b]) if value is not None else torch.zeros((), device=self.device)
                 (ce + value_coeff * vloss).backward()
-                agree = (logits.detach().argmax(-1) == expert[b]).float().mean()
                 tot += torch.stack([ce.detach(), vloss.detach(), agree])
                 updates += 1
                 nn.utils.clip_grad_norm_(params, self.max_grad_norm)

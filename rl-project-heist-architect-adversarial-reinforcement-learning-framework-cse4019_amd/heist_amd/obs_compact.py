@@ -21,6 +21,15 @@ def record_words(rows: int, cols: int) -> int:
     return b // 4
 
 
+def record_cells(records: torch.Tensor, rows: int, cols: int) -> torch.Tensor:
+    """The Solver's cell of each record, [..., 2] int32 (row, col), from the records' position word
+    (word ceil(rows * cols / 32): row | col << 8): the decision records of a rollout give
+    HeistEnv.plan_q's pos directly.  rows and cols are needed because the padded record width does
+    not determine the position word's index.  Pure torch, any device."""
+    word = records[..., (int(rows) * int(cols) + 31) // 32]
+    return torch.stack([word & 0xFF, (word >> 8) & 0xFF], -1).to(torch.int32)
+
+
 class CompactObs:
     """M observation records: records [M, W] int32, rec_env [M] int32 (each record's env), the
     grid snapshot [n_envs, R, C] int8 they were packed under, (rows, cols, vault) and an optional

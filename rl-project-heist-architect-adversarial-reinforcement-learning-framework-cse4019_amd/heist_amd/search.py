@@ -17,6 +17,9 @@ play_table restates heist_plan_play (HeistEnv.plan_play) in pure torch on CPU te
 per env played from per-tick tables, optionally perturbed by counter-hashed uniform actions.
 expert_data / expert_rollout turn such a play into exactly labelled decision states (ExpertData)
 for SolverAgent.imitation_update.
+
+q_values restates heist_plan_q (HeistEnv.plan_q) in pure torch on any device: the five exact action
+values of visited states, their maximum, the set of optimal actions and the gap of the action taken.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -424,6 +427,90 @@ def play_table(table, vis, grid, tick, pos, max_steps, initial_dist, vault, rewa
     return out
 
 
+# ---- planner Q (heist_plan_q, include/heist.h) in pure torch
+
+def q_values(values, vis, grid, tick0, pos, max_steps, initial_dist, vault, reward_consts=(-0.01, -1.0, 10.0),
+             gamma=1.0, taken=None):
+    """heist_plan_q's contract (include/heist.h) in pure torch on any device, with the handle's share
+    passed in: values [H, N, R, C] float64, vis [H, N, W] int32, grid [N, R, C] int8 (1 = wall),
+    tick0 [N] each env's tick when the tables were made (-1: done then), pos [K, N, 2] the visited
+    cells, max_steps, initial_dist [N], vault (row, col), reward_consts (step, detection, vault),
+    taken [K, N] or None.  Returns a PlanQ equal to HeistEnv.plan_q's on the same tensors, float64
+    bit for bit: every reward line is one IEEE double operation, in the header's order."""
+    from .vec_env import PlanQ
+    vt = torch.as_tensor(values)
+    dev = vt.device
+    H, N = int(vt.shape[0]), int(vt.shape[1])
+    walls = torch.as_tensor(grid, device=dev).reshape(N, *vt.shape[2:]) == 1
+    R, C = int(walls.shape[1]), int(walls.shape[2])
+    RC = R * C
+    vt, walls = vt.reshape(H, N, RC), walls.reshape(N, RC)
+    vis = torch.as_tensor(vis, device=dev)
+    pos = torch.as_tensor(pos, device=dev).to(torch.int64)
+    if pos.dim() != 3 or tuple(pos.shape[1:]) != (N, 2) or not 1 <= pos.shape[0] <= H:
+        raise ValueError("q_values: pos must be [K, %d, 2] with 1 <= K <= %d" % (N, H))
+    K = int(pos.shape[0])
+    t0 = torch.as_tensor(tick0, device=dev).to(torch.int64).reshape(1, N)
+    D0 = torch.as_tensor(initial_dist, device=dev).to(torch.int64).reshape(1, N)
+    r_step, r_detect, r_vault = (float(v) for v in reward_consts)
+    g = float(gamma)
+    vr, vc = int(vault[0]), int(vault[1])
+    k = torch.arange(K, device=dev).reshape(K, 1).expand(K, N)
+    n = torch.arange(N, device=dev).reshape(1, N).expand(K, N)
+    HK = torch.clamp(torch.clamp(int(max_steps) - t0, max=H), min=0)
+    HK = torch.where(t0 < 0, torch.zeros_like(HK), HK)
+    r, c = pos[..., 0], pos[..., 1]
+    inside = (r >= 0) & (r < R) & (c >= 0) & (c < C)
+    r, c = torch.where(inside, r, torch.zeros_like(r)), torch.where(inside, c, torch.zeros_like(c))
+    x = r * C + c
+    live = (k < HK) & inside & ~walls[n, x]
+    last = (t0 + k + 1) >= int(max_steps)
+    bonus = D0 > 3
+    denom = torch.clamp(D0, min=1).to(torch.float64)
+    dx = (r - vr).abs() + (c - vc).abs()
+    kn = (k + 1).clamp(max=H - 1)
+    qs = []
+    for a in range(N_ACTIONS):
+        yr, yc = r + DELTA[a][0], c + DELTA[a][1]
+        ok = (yr >= 0) & (yr < R) & (yc >= 0) & (yc < C)
+        yr, yc = yr.clamp(0, R - 1), yc.clamp(0, C - 1)
+        ok = ok & ~walls[n, yr * C + yc]
+        yr, yc = torch.where(ok, yr, r), torch.where(ok, yc, c)
+        y = yr * C + yc
+        curr = (yr - vr).abs() + (yc - vc).abs()
+        rew = torch.full((K, N), r_step, dtype=torch.float64, device=dev)
+        rew = rew + (dx - curr).to(torch.float64) * 0.1
+        rew = torch.where((curr <= 3) & bonus, rew + 0.05 * (3 - curr).to(torch.float64), rew)
+        seen = ((vis[k, n, y >> 5].to(torch.int64) >> (y & 31)) & 1).bool()
+        rew = torch.where(seen, rew + r_detect, rew)
+        atv = (yr == vr) & (yc == vc)
+        rew = torch.where(atv, rew + r_vault, rew)
+        frac = 1.0 - curr.to(torch.float64) / denom
+        frac = torch.where(frac < 0, torch.zeros_like(frac), frac)
+        rew = torch.where(last, rew + frac * 2.0, rew)
+        nxt = torch.where(k + 1 < H, vt[kn, n, y], torch.zeros_like(rew))
+        on = rew + g * nxt
+        qs.append(torch.where(seen | atv | last, rew, on))
+    value, best = qs[0], torch.zeros((K, N), dtype=torch.int8, device=dev)
+    for a in range(1, N_ACTIONS):
+        better = qs[a] > value  # strict: the first maximum stays
+        value = torch.where(better, qs[a], value)
+        best = torch.where(better, torch.full_like(best, a), best)
+    optimal = torch.zeros((K, N), dtype=torch.uint8, device=dev)
+    for a in range(N_ACTIONS):
+        optimal = optimal | ((qs[a] == value).to(torch.uint8) << a)
+    q = torch.stack(qs, -1)
+    zero = torch.zeros_like(value)
+    gap = None
+    if taken is not None:
+        tk = torch.as_tensor(taken, device=dev).to(torch.int64).reshape(K, N)
+        tk = torch.where((tk < 0) | (tk > 4), torch.zeros_like(tk), tk)
+        gap = torch.where(live, value - q.gather(2, tk.unsqueeze(-1)).squeeze(-1), zero)
+    return PlanQ(torch.where(live.unsqueeze(-1), q, torch.zeros_like(q)), torch.where(live, value, zero),
+                 torch.where(live, best, torch.full_like(best, -1)),
+                 torch.where(live, optimal, torch.zeros_like(optimal)), gap)
+
+
 @dataclass
 class ExpertData:
     """Decision states of a table playout, [H, N] time-major: decision k of env e is the state the
@@ -432,7 +519,8 @@ class ExpertData:
         k >= 1: the play's record k - 1);
     expert [H, N] int8 -- the table's action there (-1: none), value [H, N] float64 or None -- the
         table's value there, taken [H, N] int64 -- the action the play took;
-    valid [H, N] bool, length [N] int32; grid [N, R, C] int8 -- the tile map the records expand by."""
+    valid [H, N] bool, length [N] int32; grid [N, R, C] int8 -- the tile map the records expand by;
+    optimal [H, N] uint8 or None -- the set of optimal actions there as a bit mask (PlanQ.optimal)."""
     records: torch.Tensor
     expert: torch.Tensor
     value: Optional[torch.Tensor]
@@ -443,6 +531,7 @@ class ExpertData:
     rows: int
     cols: int
     vault: tuple
+    optimal: Optional[torch.Tensor] = None
 
     def flat(self, mask=None):
         """The valid decisions (of the envs mask [N] bool selects; None: all) as (CompactObs, expert
@@ -457,6 +546,17 @@ class ExpertData:
         obs = CompactObs(self.records.reshape(H * N, -1)[idx], env, self.grid, self.rows, self.cols, self.vault)
         value = None if self.value is None else self.value.reshape(-1)[idx].to(torch.float32)
         return obs, self.expert.reshape(-1)[idx].to(torch.int64), value, self.taken.reshape(-1)[idx]
+
+    def flat_optimal(self, mask=None):
+        """flat(mask)'s four values plus the optimal sets of the same decisions, [M] uint8 (None
+        when the data has none): SolverAgent.imitation_update's optimal."""
+        out = self.flat(mask)
+        if self.optimal is None:
+            return out + (None,)
+        keep = self.valid
+        if mask is not None:
+            keep = keep & torch.as_tensor(mask, device=keep.device).bool().reshape(1, -1)
+        return out + (self.optimal.reshape(-1)[keep.reshape(-1).nonzero().reshape(-1)],)
 
 
 def expert_data(play, records0, grid, rows, cols, vault) -> ExpertData:

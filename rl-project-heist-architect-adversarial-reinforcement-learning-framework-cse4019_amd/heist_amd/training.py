@@ -722,9 +722,23 @@ class AdversarialTrainer:  # training.py:115-790
         of every iteration.  Single-process only: imitation_update does not average gradients
         across ranks."""
         from .search import expert_rollout
-        from .vec_env import LayoutBatch
+        pe, n_envs = self._pretrain_handle(n_envs, "pretrain_solver")
+        out = []
+        for it in range(iterations):
+            valid = self._pretrain_layouts(pe, layouts, "pretrain_solver")
+            data = expert_rollout(pe, gamma=self.solver.gamma, noise=noise, seed=seed + it)
+            obs, expert, value, _ = data.flat(valid)
+            m = self.solver.imitation_update(obs, expert, value, minibatch=self.minibatch)
+            m["pretrain_valid_envs"] = int(valid.sum())
+            out.append(m)
+        return out
+
+    def _pretrain_handle(self, n_envs: Optional[int], what: str):
+        """pretrain_solver's / dagger_solver's private HeistEnv (kept between calls while n_envs
+        stays) and its size: n_envs defaults to the trainer's, cut so that the value table
+        (8 H N R C bytes) stays under 1 GB."""
         if dist_utils.is_multi():
-            raise RuntimeError("pretrain_solver: not collective; pre-train on one rank and broadcast the weights")
+            raise RuntimeError("%s: not collective; pre-train on one rank and broadcast the weights" % what)
         cfg = self.config
         R, C, H = cfg.grid_rows, cfg.grid_cols, min(int(cfg.max_steps), 1024)
         if n_envs is None:
@@ -736,31 +750,113 @@ class AdversarialTrainer:  # training.py:115-790
             pe = HeistEnv(n_envs, cfg, max_cams=self.env.max_cams, max_guards=self.env.max_guards,
                           max_path=self.env.max_path, device=self.device, auto_reset=False)
             self._pretrain_env = pe
+        return pe, n_envs
+
+    def _pretrain_layouts(self, pe, layouts, what: str) -> torch.Tensor:
+        """Fresh layouts on the private handle, then a reset: "architect" (the Architect's samples at
+        the current curriculum phase and temperature, not recorded), "empty", or a LayoutBatch sized
+        for the handle.  Returns valid [N] bool (the BFS check)."""
+        from .vec_env import LayoutBatch
+        cfg, n_envs = self.config, pe.n_envs
+        if isinstance(layouts, LayoutBatch):
+            valid = pe.set_layout_batch(layouts)
+        elif layouts == "empty":
+            valid = pe.set_layouts([([], [], [])] * n_envs, budget=cfg.architect_budget)
+        elif layouts == "architect":
+            ep = self.global_episode + 1
+            _, budget, cams, guards, _ = self.get_curriculum_phase(ep)
+            saved = self.architect.budget
+            self.architect.budget = budget
+            try:
+                lb, _, _ = self.architect.generate_layouts(n_envs, self._temperature(ep), cams, guards, env=pe,
+                                                           record=False)
+            finally:
+                self.architect.budget = saved
+            valid = pe.set_layout_batch(lb)
+        else:
+            raise ValueError("%s: layouts must be 'architect', 'empty' or a LayoutBatch" % what)
+        valid = valid.bool()
+        pe.reset()
+        return valid
+
+    # -- on-policy exact labels (DAgger; no reference counterpart) ------------------------------
+    def dagger_solver(self, iterations: int, n_envs: Optional[int] = None, beta: float = 0.0, seed: int = 0,
+                      layouts="architect", update: bool = True, horizon: Optional[int] = None) -> List[Dict[str, float]]:
+        """The on-policy counterpart of pretrain_solver, on the same private handle: each iteration
+        sets fresh layouts (as pretrain_solver does), resets, makes the value tables
+        (plan_value(all_ticks=True) at the Solver's gamma), rolls the Solver's OWN policy out on
+        that handle -- solver.act from a zero hidden state of its own, no auto-reset, until every
+        BFS-valid env is done or the horizon ends; on a share beta of the steps the table's action
+        at the current cell is taken instead -- and labels every state the rollout visited with one
+        plan_q launch: the set of optimal actions, the optimal return and the gap of the action
+        taken.  With update=True one SolverAgent.imitation_update follows on the valid decisions,
+        towards the optimal sets with the optimal return as the value target; update=False is the
+        evaluation mode, which changes no parameter and no optimizer state.  Per iteration:
+        dagger_optimal_rate (the share of valid decisions whose action is in the optimal set),
+        dagger_gap_mean (mean V*(s) - Q*(s, a_taken) per decision), dagger_regret_mean (mean over
+        valid envs of the start cell's optimal return minus search.discounted_return of the
+        rollout), dagger_discounted_gap_mean (mean over valid envs of the sum of gamma^k gap_k: the
+        regret again, by the telescoping sum, up to rounding), dagger_decisions,
+        pretrain_valid_envs and, when updating, the imitation_* keys.  The draws (the policy's samples on the fp32 path, the beta mixing) come from a generator
+        seeded with seed + iteration.  The trainer's env batch, LSTM state, counters, logs and
+        the Architect are left as they were.  Single-process only, as pretrain_solver is."""
+        from .obs_compact import record_cells
+        from .search import ExpertData, discounted_return
+        if not 0.0 <= float(beta) <= 1.0:
+            raise ValueError("dagger_solver: beta must be in [0, 1]")
+        pe, n_envs = self._pretrain_handle(n_envs, "dagger_solver")
+        cfg, dev = self.config, self.device
+        R, C = cfg.grid_rows, cfg.grid_cols
+        H = min(int(cfg.max_steps), 1024) if horizon is None else int(horizon)
+        W = record_words(R, C)
+        env_ids = torch.arange(n_envs, device=dev)
         out = []
         for it in range(iterations):
-            if isinstance(layouts, LayoutBatch):
-                valid = pe.set_layout_batch(layouts)
-            elif layouts == "empty":
-                valid = pe.set_layouts([([], [], [])] * n_envs, budget=cfg.architect_budget)
-            elif layouts == "architect":
-                ep = self.global_episode + 1
-                _, budget, cams, guards, _ = self.get_curriculum_phase(ep)
-                saved = self.architect.budget
-                self.architect.budget = budget
-                try:
-                    lb, _, _ = self.architect.generate_layouts(n_envs, self._temperature(ep), cams, guards, env=pe,
-                                                               record=False)
-                finally:
-                    self.architect.budget = saved
-                valid = pe.set_layout_batch(lb)
-            else:
-                raise ValueError("pretrain_solver: layouts must be 'architect', 'empty' or a LayoutBatch")
-            valid = valid.bool()
-            pe.reset()
-            data = expert_rollout(pe, gamma=self.solver.gamma, noise=noise, seed=seed + it)
-            obs, expert, value, _ = data.flat(valid)
-            m = self.solver.imitation_update(obs, expert, value, minibatch=self.minibatch)
-            m["pretrain_valid_envs"] = int(valid.sum())
+            valid = self._pretrain_layouts(pe, layouts, "dagger_solver")
+            pv = pe.plan_value(horizon=H, gamma=self.solver.gamma, all_ticks=True)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(int(seed) + it)
+            rec = torch.zeros((H, n_envs, W), dtype=torch.int32, device=dev)
+            taken = torch.zeros((H, n_envs), dtype=torch.int64, device=dev)
+            r64 = torch.zeros((H, n_envs), dtype=torch.float64, device=dev)
+            done = torch.ones((H, n_envs), dtype=torch.bool, device=dev)
+            dec = torch.zeros((H, n_envs), dtype=torch.bool, device=dev)
+            alive, hidden, K = valid.clone(), None, 0
+            # the fused act() would read a seed back from the generator every tick (a host sync): it
+            # keeps its own counter-hashed draws
+            act_gen = None if self.solver.fused_inference else gen
+            with torch.no_grad():
+                for k in range(H):
+                    pe.pack_obs(pe.obs, out=rec[k])
+                    a, _, _, hidden = self.solver.act(pe.obs, hidden, generator=act_gen)
+                    if beta > 0.0:
+                        cell = record_cells(rec[k], R, C).long()
+                        t = pv.action_ticks[k, env_ids, cell[:, 0], cell[:, 1]].long().clamp(min=0)
+                        a = torch.where(torch.rand(n_envs, device=dev, generator=gen) < beta, t, a)
+                    _, _, d, _ = pe.step(a, auto_reset=False)
+                    taken[k], r64[k], done[k], dec[k] = a, pe.reward64, d, alive
+                    alive = alive & ~d
+                    K = k + 1
+                    if k % 8 == 7 and not bool(alive.any()):  # the one host sync, every 8 ticks
+                        break
+            rec, taken, r64, done, dec = rec[:K], taken[:K], r64[:K], done[:K], dec[:K]
+            pq = pe.plan_q(pv, record_cells(rec, R, C), taken)
+            nd = int(dec.sum())
+            nv = int(valid.sum())
+            regret = pq.value[0] - discounted_return(r64, done, self.solver.gamma)
+            disc = torch.full((K, 1), float(self.solver.gamma), dtype=torch.float64, device=dev) ** \
+                torch.arange(K, dtype=torch.float64, device=dev).reshape(K, 1)
+            gap_sum = (torch.where(dec, pq.gap, torch.zeros_like(pq.gap)) * disc).sum(0)
+            m = {"dagger_optimal_rate": float((pq.gap[dec] == 0.0).double().mean()) if nd else 0.0,
+                 "dagger_gap_mean": float(pq.gap[dec].mean()) if nd else 0.0,
+                 "dagger_regret_mean": float(regret[valid].mean()) if nv else 0.0,
+                 "dagger_discounted_gap_mean": float(gap_sum[valid].mean()) if nv else 0.0,
+                 "dagger_decisions": nd, "pretrain_valid_envs": nv}
+            if update:
+                data = ExpertData(rec, pq.best, pq.value, taken, dec, dec.sum(0).to(torch.int32), pv.grid, R, C,
+                                  (int(cfg.vault_pos[0]), int(cfg.vault_pos[1])), pq.optimal)
+                obs, expert, value, _, optimal = data.flat_optimal()
+                m.update(self.solver.imitation_update(obs, expert, value, minibatch=self.minibatch, optimal=optimal))
             out.append(m)
         return out
 

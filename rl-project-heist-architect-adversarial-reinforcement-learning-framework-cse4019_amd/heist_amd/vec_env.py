@@ -164,7 +164,9 @@ class PlanValue:
         env's ticks; with all_ticks=True only;
     vault -- the vault's (row, col); gamma -- the discount the values were computed with;
     grid [N, R, C] int8 -- the tile map (export(grid=True)), whose walls
-        heist_amd.search.follow_value moves by."""
+        heist_amd.search.follow_value moves by;
+    tick [N] int32 or None -- each env's tick when the tables were made, -1 where it was done
+        then: HeistEnv.plan_q's tick0, which labels a rollout after the handle has been stepped."""
     value: torch.Tensor
     action: torch.Tensor
     vis: torch.Tensor
@@ -175,8 +177,28 @@ class PlanValue:
     vault: Optional[Tuple[int, int]] = None
     gamma: float = 1.0
     grid: Optional[torch.Tensor] = None
+    tick: Optional[torch.Tensor] = None
 
     vis_mask = PlanField.vis_mask
+
+
+@dataclass
+class PlanQ:
+    """HeistEnv.plan_q's output (heist_plan_q, include/heist.h; heist_amd.search.q_values gives the
+    same on any device): the exact action values of visited states, [K, N] time-major, state
+    (k, e) being the cell env e's Solver stands on k ticks after the tables were made.
+    q [K, N, 5] float64 -- the optimal discounted return after taking action a there;
+    value [K, N] float64, best [K, N] int8 -- their maximum and its first action (the tables' own
+        value and action at that state);
+    optimal [K, N] uint8 -- bit a is set iff q[a] equals value exactly: the set of optimal actions;
+    gap [K, N] float64 or None -- value - q[taken], exactly 0.0 iff the taken action is optimal.
+    A state that is not live (past the env's steps, off the grid, a wall cell) holds 0.0, best -1
+    and an empty set.  An output that was not asked for is None."""
+    q: Optional[torch.Tensor]
+    value: Optional[torch.Tensor]
+    best: Optional[torch.Tensor]
+    optimal: Optional[torch.Tensor]
+    gap: Optional[torch.Tensor]
 
 
 @dataclass
@@ -517,8 +539,78 @@ class HeistEnv:
         with torch.cuda.device(self.device):
             nat.check(nat.lib().heist_plan_value(self._h, H, float(gamma), nat.ptr(value), nat.ptr(action), nat.ptr(vis),
                                                  nat.ptr(vticks), nat.ptr(aticks), self._stream()), "heist_plan_value")
+        ex = self.export(grid=True)
+        tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
         return PlanValue(value, action, vis, vticks, aticks, R, C, tuple(int(v) for v in self.config.vault_pos),
-                         float(gamma), self.export(grid=True)["grid"])
+                         float(gamma), ex["grid"], tick)
+
+    # -- planner Q (heist_plan_q) --------------------------------------------------------------
+    PLAN_Q_OUTPUTS = ("q", "value", "best", "optimal", "gap")
+
+    def plan_q(self, pv, pos: torch.Tensor, taken: Optional[torch.Tensor] = None,
+               tick0: Optional[torch.Tensor] = None, gamma: Optional[float] = None,
+               outputs: Optional[Sequence[str]] = None) -> "PlanQ":
+        """heist_plan_q: the five exact action values of every visited state in one launch that
+        casts no ray and touches no env.  pv: a PlanValue made with all_ticks=True, or a
+        (values [H, N, R, C] float64, vis [H, N, W] int32) pair of hand-made tables; pos [K, N, 2]
+        (row, col) with K <= H, row k the Solver's cell k ticks after the tables were made
+        (obs_compact.record_cells gives it from a rollout's decision records); taken [K, N] the
+        action taken there, or None (then there is no gap).  tick0 [N]: each env's tick when the
+        tables were made, -1 for an env done then; it defaults to pv.tick for a PlanValue, and for
+        a pair to None, the handle's tick and done flag as they are now -- right only while the
+        handle has not been stepped since.  gamma defaults to pv.gamma (1.0 for a pair).  outputs:
+        the PlanQ fields to compute (default all; gap only with taken).  The handle's layout must
+        be the one the tables were made for.  Reads the envs only."""
+        from .obs_compact import record_words
+        n, R, C = self.n_envs, self.rows, self.cols
+        W = record_words(R, C)
+        dev = self.device
+        if isinstance(pv, PlanValue):
+            if pv.value_ticks is None:
+                raise ValueError("plan_q: the value has no per-tick rows (plan_value(all_ticks=True))")
+            values, vis = pv.value_ticks, pv.vis
+            gamma = pv.gamma if gamma is None else gamma
+            tick0 = pv.tick if tick0 is None else tick0
+        else:
+            values, vis = pv
+            gamma = 1.0 if gamma is None else gamma
+        H = int(values.shape[0]) if values.dim() else 0
+
+        def arg(t, dtype, shape, what, align=1):
+            if tuple(t.shape) != shape or t.dtype != dtype:
+                raise ValueError("plan_q: %s must be a %s %s tensor" % (what, dtype, shape))
+            if t.device != dev or not t.is_contiguous() or t.data_ptr() % align:
+                t = t.to(dev).contiguous()
+                if t.data_ptr() % align:
+                    t = t.clone()
+            return t
+        values = arg(values, torch.float64, (H, n, R, C), "values", 8)
+        vis = arg(vis, torch.int32, (H, n, W), "vis", 16)
+        pos = torch.as_tensor(pos)
+        if pos.dim() != 3 or tuple(pos.shape[1:]) != (n, 2):
+            raise ValueError("plan_q: pos must be [K, %d, 2]" % n)
+        K = int(pos.shape[0])
+        pos = pos.to(device=dev, dtype=torch.int32).contiguous()
+        if taken is not None:
+            taken = torch.as_tensor(taken).to(device=dev, dtype=torch.int64).reshape(K, n).contiguous()
+        if tick0 is not None:
+            tick0 = torch.as_tensor(tick0).to(device=dev, dtype=torch.int32).reshape(n).contiguous()
+        names = self.PLAN_Q_OUTPUTS if outputs is None else tuple(outputs)
+        if any(name not in self.PLAN_Q_OUTPUTS for name in names):
+            raise ValueError("plan_q: outputs must be among %s" % (self.PLAN_Q_OUTPUTS,))
+        if outputs is None and taken is None:
+            names = tuple(name for name in names if name != "gap")
+        kw = dict(device=dev)
+        shapes = {"q": ((K, n, 5), torch.float64), "value": ((K, n), torch.float64), "best": ((K, n), torch.int8),
+                  "optimal": ((K, n), torch.uint8), "gap": ((K, n), torch.float64)}
+        out = PlanQ(*(torch.empty(shapes[f][0], dtype=shapes[f][1], **kw) if f in names else None
+                      for f in self.PLAN_Q_OUTPUTS))
+        P = nat.ptr
+        with torch.cuda.device(dev):
+            nat.check(nat.lib().heist_plan_q(self._h, H, K, float(gamma), P(values), P(vis), P(tick0), P(pos), P(taken),
+                                             P(out.q), P(out.value), P(out.best), P(out.optimal), P(out.gap),
+                                             self._stream()), "heist_plan_q")
+        return out
 
     # -- planner playout (heist_plan_play) ---------------------------------------------------
     def plan_play(self, table: torch.Tensor, vis: torch.Tensor, values: Optional[torch.Tensor] = None,

@@ -26,6 +26,12 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # to the path it replaces (follow_value + step_multi_records on a
                                                  # twin handle restored from the saved state + value_targets) and to
                                                  # heist_plan_value itself; also written to profiles/plan_play.log
+  python tools/plan_env.py --q [--noise P] [--gamma G]
+                                                 # the planner Q (heist_plan_q, HeistEnv.plan_q) on the states of a
+                                                 # noisy table play, K = horizon, on the three batches: the launch,
+                                                 # search.q_values on the same device tensors and the
+                                                 # plan_value(all_ticks=True) launch that makes its inputs; also
+                                                 # written to profiles/plan_q.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -268,6 +274,81 @@ def play_table_mode(args, dev):
         fh.write(line + "\n")
 
 
+def q_mode(args, dev):
+    """heist_plan_q next to its restatement in torch (search.q_values on the same device tensors) and
+    to the plan_value(all_ticks=True) launch that makes its inputs, same process, same handle (all
+    of them only read it): one JSON line per batch.  The states are those of a noisy table play
+    (plan_play at --noise), K = horizon rows."""
+    from heist_amd.obs_compact import record_cells
+    from heist_amd.search import q_values
+    H = min(args.horizon or args.max_steps, 1024)
+    N, R = args.envs, args.grid
+    lines = []
+    for kind in ("architect", "empty", "synthetic"):
+        env = make_env(args, kind, dev)
+        kc = env.kernel_config()
+        assert env.plan_value_supported == 1, kc
+        cfg = env.config
+        pv = env.plan_value(H, gamma=args.gamma, all_ticks=True)
+        play = env.plan_play(pv.action_ticks, pv.vis, noise=args.noise, seed=args.seed)
+        x = env.export()
+        start = torch.stack([x["pos_r"], x["pos_c"]], 1).to(torch.int32).unsqueeze(0)
+        pos = torch.cat([start, record_cells(play.records, R, R)[:-1]]).contiguous()
+        taken = play.actions
+        valid = torch.arange(H, device=dev).reshape(H, 1) < play.length.reshape(1, N)
+        consts = (cfg.reward_step, cfg.reward_detection, cfg.reward_vault)
+
+        def torch_path():
+            return q_values(pv.value_ticks, pv.vis, pv.grid, pv.tick, pos, cfg.max_steps, x["initial_dist"],
+                            cfg.vault_pos, consts, gamma=args.gamma, taken=taken)
+
+        got, ref = env.plan_q(pv, pos, taken), torch_path()
+        same = all(torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a,
+                               b.view(torch.int64) if b.dtype == torch.float64 else b)
+                   for a, b in ((getattr(got, f), getattr(ref, f)) for f in env.PLAN_Q_OUTPUTS))
+        sets = torch.zeros_like(got.optimal, dtype=torch.int64)
+        for a in range(5):
+            sets += (got.optimal.long() >> a) & 1
+        nd = max(1, int(valid.sum()))
+        out = {"config": "%dx%d" % (R, R), "envs": N, "layouts": kind, "horizon": H, "K": H, "gamma": args.gamma,
+               "noise": args.noise, "multi_waves": kc["multi_waves"], "states": H * N, "valid_decisions": int(valid.sum()),
+               "kernel_equals_q_values_bitwise": bool(same),
+               "optimal_rate": float((got.gap[valid] == 0.0).sum()) / nd, "gap_mean": float(got.gap[valid].sum()) / nd,
+               "optimal_set_size_mean": float(sets[valid].sum()) / nd,
+               "decisions_with_several_optimal_actions_frac": float((sets[valid] >= 2).sum()) / nd}
+        del got, ref
+        ms = timed(dev, lambda: env.plan_q(pv, pos, taken), args.warmup, args.runs)
+        out["plan_q"] = {"launch_ms_median": statistics.median(ms), "launch_ms": ms,
+                         "ns_per_state": statistics.median(ms) * 1e6 / (H * N)}
+        ms = timed(dev, lambda: env.plan_q(pv, pos, taken, outputs=("optimal", "gap")), args.warmup, args.runs)
+        out["plan_q_optimal_gap_only"] = {"launch_ms_median": statistics.median(ms), "launch_ms": ms}
+        # the launch alone: 20 back-to-back ctypes calls on buffers made once, between two events,
+        # so the host's share of one plan_q() call (allocations, argument checks) is not in it
+        from heist_amd import _native as nat
+        bufs = env.plan_q(pv, pos, taken)
+        fn, P = nat.lib().heist_plan_q, nat.ptr
+        raw = (env._h, H, H, float(args.gamma), P(pv.value_ticks), P(pv.vis), P(pv.tick), P(pos), P(taken), P(bufs.q),
+               P(bufs.value), P(bufs.best), P(bufs.optimal), P(bufs.gap), env._stream())
+        ms = [m / 20 for m in timed(dev, lambda: [fn(*raw) for _ in range(20)], args.warmup, args.runs)]
+        out["plan_q_launch_alone"] = {"launch_ms_median": statistics.median(ms), "launch_ms": ms,
+                                      "ns_per_state": statistics.median(ms) * 1e6 / (H * N)}
+        ms = timed(dev, torch_path, args.warmup, args.runs)
+        out["torch_q_values"] = {"ms_median": statistics.median(ms), "ms": ms}
+        ms = timed(dev, lambda: env.plan_value(H, gamma=args.gamma, all_ticks=True), args.warmup, args.runs)
+        out["plan_value_all_ticks"] = {"launch_ms_median": statistics.median(ms), "launch_ms": ms}
+        q = out["plan_q"]["launch_ms_median"]
+        out["torch_q_values_over_plan_q"] = out["torch_q_values"]["ms_median"] / q
+        out["plan_q_over_plan_value_all_ticks"] = q / out["plan_value_all_ticks"]["launch_ms_median"]
+        env.close()
+        lines.append(json.dumps(out))
+        print(lines[-1], flush=True)
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_q.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --q --noise %r --gamma %r\n" % (args.noise, args.gamma))
+        fh.write("\n".join(lines) + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -291,12 +372,16 @@ def main(argv=None):
     ap.add_argument("--gamma", type=float, default=1.0, help="with --value: the discount")
     ap.add_argument("--play", action="store_true", help="time heist_plan_play next to the Python path it replaces and "
                     "to heist_plan_value on the --layouts batch")
-    ap.add_argument("--noise", type=float, default=0.1, help="with --play: the noisy configurations' probability")
+    ap.add_argument("--noise", type=float, default=0.1, help="with --play / --q: the noisy play's probability")
+    ap.add_argument("--q", action="store_true", help="time heist_plan_q next to search.q_values on the same device "
+                    "tensors and to the plan_value(all_ticks=True) launch that feeds it, on all three batches")
     ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
-                    "profiles/plan_play.log)")
+                    "profiles/plan_play.log, --q's: profiles/plan_q.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.q:
+        return q_mode(args, dev)
     if args.play:
         return play_table_mode(args, dev)
     if args.value:

@@ -3,12 +3,13 @@
 # usage: tools/regs.sh [regex]   (default: step|reset|cones; `plan` the planner's and the planner
 #        field's instances, `field` plan_field_kernel's alone, `value` plan_value_kernel's alone)
 #        tools/regs.sh play      plan_play_kernel (heist_play.hip), with its SGPRs and LDS
+#        tools/regs.sh q         plan_q_kernel (heist_q.hip), the same columns
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 CSRC=$ROOT/rl-project-heist-architect-adversarial-reinforcement-learning-framework-cse4019_amd/csrc
 OUT=$(mktemp -d)
-if [ "$1" = "play" ]; then
+if [ "$1" = "play" ] || [ "$1" = "q" ]; then
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC -ffp-contract=off -fno-fast-math --offload-arch=gfx950 \
-    -I "$ROOT/include" -I "$CSRC" -c "$CSRC/heist_play.hip" -o "$OUT/hp.o" -Rpass-analysis=kernel-resource-usage \
+    -I "$ROOT/include" -I "$CSRC" -c "$CSRC/heist_$1.hip" -o "$OUT/hp.o" -Rpass-analysis=kernel-resource-usage \
     > "$OUT/res.txt" 2>&1 || { grep -E "error" "$OUT/res.txt" | head -20; exit 1; }
   grep -E "remark: +(Function Name|TotalSGPRs:|VGPRs:|Occupancy|SGPRs Spill|VGPRs Spill|ScratchSize|LDS Size)" "$OUT/res.txt" \
     | sed 's/.*remark: *//; s/ \[-Rpass.*//' | paste - - - - - - - - | sed 's/Function Name: _ZN5heist[0-9_A-Za-z]*N_1[0-9]*//; s/ENS_[^\t]*//'
