@@ -3342,9 +3342,10 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   // HBM data a tick needs -- its shared fan entry (FanTick: the unique directions' sample
   // tiles, n_uniq, n_tie) and its cached guards' cone entries -- comes by LDS-DMA issued a
   // tick ahead: the fan entry once the tick has marched its own (the staging is then free),
-  // a cone entry once the guard's move is known (the pose after the next move, and with it
-  // the entry a reset at that tick restamps: patrol point 0 at the same heading slot; a
-  // finishing env re-issues both from its reset pose; double-buffered by tick parity).  So no
+  // a cone entry once the tick knows the pose the env leaves it in (the guard's move, then the
+  // reset if the episode ends: the pose after the next move from there, and with it the entry
+  // a reset at that tick stamps: patrol point 0 at the same heading slot; one issue per tick,
+  // double-buffered by tick parity).  So no
   // tick waits for a global load of its own.  The tick's stores
   // go last, so the next tick's counted wait for the DMA (kStores younger operations)
   // never waits for a store to reach memory.
@@ -3445,9 +3446,9 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     }
   };
   // this tick's visibility: into the cleared plane every camera marches the shared fan's
-  // unique directions from the staging, with the table's near-tie rays on the exact path;
-  // the cached cones go into the guard plane
-  auto cast_fan = [&](int k, int n_uniq, int n_tie, int par, bool staged_wide) {
+  // unique directions from the staging, with the table's near-tie rays on the exact path
+  // (the cached cones go into the guard plane once the tick knows which pose its row shows)
+  auto cast_fan = [&](int k, int n_uniq, int n_tie, bool staged_wide) {
 #pragma unroll
     for (int z = 0; z < D / 1024; ++z)  // 64 x 16 B per pass: the plane
       reinterpret_cast<uint4*>(vis)[lane + 64 * z] = make_uint4(0u, 0u, 0u, 0u);
@@ -3488,8 +3489,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
       if (n_tie > 0) lean_tie_rays<D, PC>(smem, f, n_tie, cam_rc, s.n_cams, p.half_deg);
     }
-    LEAN_STAMP(2);
-    stamp_cones(L.cone, par);
   };
   // this tick's visibility from the interval table (an env the shared fan does not serve).
   // Ray i of a camera lies i * su angle units past its fixed-point start h0 (the reference's
@@ -3511,7 +3510,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
   auto wave_join = [&]() {
     if constexpr (NW == 2) asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
   };
-  auto cast_ivl = [&](int par) {
+  auto cast_ivl = [&]() {
     wave_join();  // both waves' reads of the previous plane are done
 #pragma unroll
     for (int z = wid; z < D / 1024; z += NW)  // 64 x 16 B per pass: the plane
@@ -3589,16 +3588,14 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
       if (safe) march_at(cu.z >> 16, dj);
     }
-    LEAN_STAMP(2);
-    if (wid == 0) stamp_cones(L.cone, par);
-    wave_join();  // the planes are complete
+    wave_join();  // the cameras' plane is complete
   };
-  auto cast = [&](int k, int n_uniq, int n_tie, int par, bool staged_wide) {
+  auto cast = [&](int k, int n_uniq, int n_tie, bool staged_wide) {
     if (ivl) {
-      cast_ivl(par);
+      cast_ivl();
     } else {  // the shared fan: wave 0's (its staging and DMA are wave 0's)
       wave_join();
-      if (wid == 0) cast_fan(k, n_uniq, n_tie, par, staged_wide);
+      if (wid == 0) cast_fan(k, n_uniq, n_tie, staged_wide);
       wave_join();
     }
   };
@@ -3630,7 +3627,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
     const bool staged_wide = wide;
     const bool frozen = s.done != 0;  // finished, no auto-reset: environment.py:232-233
     double reward = 0.0;
-    int status = kAlreadyDone, curr = 0;
+    int status = kAlreadyDone, curr = 0, done_now = s.done;
     if (!frozen) {
       // 1. move (environment.py:239-246) and the reward terms that precede detection (:235, :261-269)
       const int a = __builtin_amdgcn_readlane((int)vact, k & 63);
@@ -3657,32 +3654,26 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
       // the slot after the guard's next move: row 15 of this tick's entry (staged a tick ago)
       if (cached && wid == 0) gd.nslot = L.cone[par * 16 * mg + 8 * mg + 8 * g + 7];
-      if (k + 1 < K && wid == 0) dma_next_cone(par ^ 1);  // tick k + 1's entry if the env still acts then
       LEAN_STAMP(1);  // 1: move, rotation, patrol
-      // 3. visibility (environment.py:257-258)
-      cast(k, n_uniq, n_tie, par, staged_wide);
-      LEAN_STAMP(3);  // 3: the cached guard cones (2: the cameras, inside cast)
-    }
-    // (tick k + 1's fan entry went out inside cast_fan; a frozen env keeps its planes and skips it)
-    wide = n_uniq > 64;
-    // the planes' channel-1 quads this wave stores (one wave: also the detection test's byte)
-    uint32_t v1[QW];
-    read_v1(v1);
-    int done_now = s.done;
-    LEAN_STAMP(4);  // 4: next fan DMA, the channel-1 quads
-    if (!frozen) {
+      // 3. the cameras' visibility (environment.py:257-258; tick k + 1's fan entry goes out
+      // inside cast_fan).  The guards' share is stamped once the tick knows which pose its row
+      // shows (5.): whether a guard sees the solver needs no plane
+      cast(k, n_uniq, n_tie, staged_wide);
+      LEAN_STAMP(2);  // 2: the cameras
+      // does a camera see the solver's tile: its byte of the plane; does a cached guard: the
+      // bit of its staged cone row that stamp_cones would set on that tile (row dr + 7 of the
+      // entry, bit dc + 7, inside the 15 x 15 window only; row 15 is the next slot).  Both
+      // reads go out together; with two waves each wave reads for itself (the staging is
+      // wave 0's DMA, landed before the cast's joins)
+      const uint32_t cam_sees = vis[OFF0 + s.pos_r * PC + s.pos_c];
+      uint32_t grow = 0;
+      const int sdr = s.pos_r - (int)unpack_r((uint16_t)gd.pos()) + kConeRange;
+      const int sdc = s.pos_c - (int)unpack_c((uint16_t)gd.pos()) + kConeRange;
+      if (cached && (unsigned)sdr <= 2u * kConeRange && (unsigned)sdc <= 2u * kConeRange)
+        grow = (L.cone[par * 16 * mg + (sdr >> 3) * 8 * mg + 8 * g + (sdr & 7)] & 0x7fffu) >> sdc;
+      const bool seen = (cam_sees | (uint32_t)(__ballot((grow & 1u) != 0u) != 0ull)) != 0u;
+      LEAN_STAMP(3);  // 3: is the solver seen
       // 4. detection, vault, timeout (environment.py:271-297), in the reference's order
-      bool seen;
-      if constexpr (NW == 1) {
-        const int sol = s.pos_r * C_ + s.pos_c, qs = sol >> 2;
-        uint32_t vq = v1[0];  // the quad holding the solver's tile (register qs >> 6, wave-uniform)
-#pragma unroll
-        for (int j = 1; j < Q; ++j) vq = (qs >> 6) == j ? v1[j] : vq;
-        const uint32_t qv = (uint32_t)__builtin_amdgcn_readlane((int)vq, qs & 63);
-        seen = ((qv >> (8 * (sol & 3))) & 0xffu) != 0u;
-      } else {  // the quad may be the other wave's: the byte itself
-        seen = (vis[OFF0 + s.pos_r * PC + s.pos_c] | L.gpl[s.pos_r * C_ + s.pos_c]) != 0;
-      }
       if (seen) {
         s.detected = 1;
         reward += p.r_detect;
@@ -3705,11 +3696,13 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       }
       done_now = s.done;
     }
-    LEAN_STAMP(5);  // 5: detection, vault, timeout
+    wide = n_uniq > 64;
+    LEAN_STAMP(4);  // 4: detection, vault, timeout
+    bool reset_moved = false;  // the row shows reset poses that differ from the tick's
     if (auto_reset && done_now) {
       // 5. auto-reset (environment.py:183-214): headings kept, guards back to patrol point 0;
-      // this row's observation is the next attempt's first one
-      const bool moved = __ballot(live_guard && gd.pos() != gd.pos0()) != 0ull;
+      // this row's observation is the next attempt's first one (the cameras' share stands)
+      reset_moved = __ballot(live_guard && gd.pos() != gd.pos0()) != 0ull;
       reset_solver(p, s);
       if (live_guard) {
         gd.a &= ~0xffu;                        // idx 0
@@ -3718,15 +3711,23 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(4))) vo
       // the cone of (patrol point 0, this slot) was staged a tick ago with the tick's own: the
       // slot after the next move from there is its row 15
       if (cached && wid == 0) gd.nslot = L.rcone[par * 16 * mg + 8 * mg + 8 * g + 7];
-      if (moved) {  // the guard plane again from the reset poses; the cameras' share stands (headings kept)
-        wave_join();  // both waves have read the tick's guard plane
-        if (wid == 0) stamp_cones(L.rcone, par);
-        wave_join();
-        read_v1(v1);
-      }
-      if (k + 1 < K && wid == 0) dma_next_cone(par ^ 1);  // tick k + 1's entry from the reset pose
     }
-    LEAN_STAMP(6);  // 6: auto-reset
+    // tick k + 1's cone entries, once, from the pose the env has now (after the reset if there
+    // was one; a frozen env needs none): a cast later than at the move, still before the tick's
+    // stores, so the next tick's counted wait covers them
+    if (!frozen && k + 1 < K && wid == 0) dma_next_cone(par ^ 1);
+    LEAN_STAMP(5);  // 5: auto-reset, the next cone entries' DMA
+    // the guards' share of the row, once: the reset poses' cones where the reset moved a guard
+    // (the entries of patrol point 0 staged with the tick's own), else the tick's; a frozen env
+    // keeps its planes
+    if (!frozen) {
+      if (wid == 0) stamp_cones(reset_moved ? L.rcone : L.cone, par);
+      wave_join();  // the guard plane is complete
+    }
+    // the planes' channel-1 quads this wave stores
+    uint32_t v1[QW];
+    read_v1(v1);
+    LEAN_STAMP(6);  // 6: the guard cones, the channel-1 quads
     // 6. tick k's stores (kStores, unconditional; lanes with nothing to store pass an offset
     // past their buffer descriptor, which the hardware drops): observation channels 0, 1, 2
     // (Q quads per lane each) or, REC, the record's words, then reward, reward64, done, status

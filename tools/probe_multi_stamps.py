@@ -22,8 +22,8 @@ from heist_amd import _native as nat  # noqa: E402
 SEGS = ["move+shaping", "emitters|static", "publish|clear", "wait_raycast_barrier", "raycast", "wait_raycast_end",
         "detect+reset", "out|ch1", "tick_end_barrier"]
 # step_lean_kernel's segments (20 x 20 / 32 x 32 one wave per env, HEIST_LEAN=1, the default)
-LEAN_SEGS = ["dma_wait+fan_hdr", "move+rotate+patrol", "cameras", "guard_cones", "fan_dma+ch1_reads",
-             "detect+vault+timeout", "auto_reset", "stores", "-"]
+LEAN_SEGS = ["dma_wait+fan_hdr", "move+rotate+patrol", "cameras+fan_dma", "seen", "detect+vault+timeout",
+             "auto_reset+cone_dma", "guard_cones+ch1_reads", "stores", "-"]
 
 
 def main():
