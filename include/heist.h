@@ -355,6 +355,56 @@ int heist_plan_value(heist_t h, int horizon, double gamma, double* value_out, in
                      uint32_t* vis_out, double* value_ticks_out, int8_t* action_ticks_out,
                      heist_stream_t stream);
 
+/* Planner what-if, no reference counterpart: heist_plan_field's fewest ticks and heist_plan_value's
+ * optimal return of every env with some of its emitters switched off -- M variants per env in one
+ * launch, which is what tells which camera or guard a layout's difficulty comes from.  Visibility is
+ * a union over the emitters, and an emitter blocks neither a ray nor a move (only wall tiles do), so
+ * "slot j is off" is defined at any tick of any env: the slot's record still advances every tick
+ * (camera heading, guard patrol index and heading), it casts no ray, stamps no cached cone and, for
+ * a guard cast live, does not mark its own cell.  The grid stays as heist_set_layout left it: a
+ * guard is placed without a placement check and its start tile replaces a wall under it, and a
+ * switched-off guard does not put that wall back (a layout rebuilt without the guard would).
+ *   emitter_mask [N][M] uint64, 8-byte aligned, M >= 1: bit j of emitter_mask[e][m] says slot j of
+ *                env e is live in variant (e, m).  Slots are numbered as everywhere else: cameras
+ *                0 .. max_cams-1, then guard g at max_cams + g.  Bits of slots the env does not fill
+ *                (camera slots from n_cams[e] up, guard slots from n_guards[e] up) and bits at or
+ *                above max_cams + max_guards are ignored.
+ * Variant (e, m) is planned from env e's current state -- its tick, its emitters' poses, its
+ * Solver's cell pos -- exactly as heist_plan_field and heist_plan_value plan it, HK = min(horizon,
+ * max_steps - tick[e]) ticks (0 for an env already done), with vis_k the union over the live slots
+ * alone; togo_0 and V_0 below are heist_plan_field's and heist_plan_value's recurrences over those
+ * vis_k, V_0 in heist_plan_value's own arithmetic (the same lines in the same order, each one IEEE
+ * double operation, none contracted, the first maximum under a strict greater-than).
+ *   ticks_out       [N][M] int16: togo_0[pos], in 1 .. 1024 or -1 (no undetected way to the vault).
+ *   value_out       [N][M] float64, 8-byte aligned: V_0[pos].
+ *   action_out      [N][M] int8: heist_plan_value's action at pos and k = 0.
+ *   vis_out         [horizon][N][M][W] uint32, W = heist_obs_record_bytes(rows, cols) / 4, 16-byte
+ *                   aligned, required (it is the backward sweeps' history): row (k-1, e, m), at
+ *                   (((k-1) N + e) M + m) W words, holds variant (e, m)'s vis_k in the record's bit
+ *                   order, padding as in heist_plan_field, rows k > HK are 0.  For M = 1 this is
+ *                   heist_plan_field's layout.
+ *   togo_cells_out  [N][M][R*C] int16 or NULL: the whole togo_0 (wall cells -1).
+ *   value_cells_out [N][M][R*C] float64 or NULL, 8-byte aligned: the whole V_0 (wall cells 0.0).
+ *                   The two optional outputs are independent of each other; there are no per-tick
+ *                   tables here.
+ * Every variant of an env with HK = 0 holds -1 / 0.0 / -1, in the cell tables too.
+ * A variant with every filled slot's bit set is heist_plan_field / heist_plan_value on the same
+ * handle, bit for bit: ticks_out = togo_out[e][pos], value_out = value_out[e][pos], action_out =
+ * heist_plan_value's action_out[e][pos], the cell tables their togo_out / value_out, the vis rows
+ * their vis_out.  A variant with no bit set is the same pair of calls on the layout's walls alone.
+ * The launch only reads the env, as heist_plan_field does.
+ * heist_plan_masked_supported: heist_plan_value_supported's value -- the kernel's LDS is
+ *   heist_plan_value's (the tick counts lie over one of the two float64 arrays): every grid up to
+ *   32 x 32 at 1, 2 and 4 K-tick waves; 64 x 64 is not supported.  -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, gamma not finite or outside [0, 1], M < 1 or N M >= 2^31,
+ * a NULL emitter_mask, ticks_out, value_out, action_out or vis_out, vis_out not 16-byte aligned,
+ * emitter_mask, value_out or value_cells_out not 8-byte aligned, a probe mode armed
+ * (HEIST_PROBE_MODE), heist_plan_masked_supported 0. */
+int heist_plan_masked_supported(heist_t h);
+int heist_plan_masked(heist_t h, int horizon, double gamma, int M, const uint64_t* emitter_mask,
+                      int16_t* ticks_out, double* value_out, int8_t* action_out, uint32_t* vis_out,
+                      int16_t* togo_cells_out, double* value_cells_out, heist_stream_t stream);
+
 /* Planner playout, no reference counterpart: one episode per env played from a planner's per-tick
  * tables -- the table's own (expert) play, or that play perturbed on a counter-hashed share of the
  * steps, every visited state still labelled by the table.  The emitters do not depend on the

@@ -7,8 +7,9 @@ hand-written HIP kernels for gfx950 behind the C ABI in include/heist.h
 __version__ = "0.1.0"
 
 from .environment import EnvironmentConfig, HeistEnvironment  # noqa: F401
-from .vec_env import HeistEnv, LayoutBatch, PlanField, PlanPlay, PlanQ, PlanResult, PlanValue, STATUS_NAMES  # noqa: F401
+from .vec_env import (HeistEnv, LayoutBatch, PlanField, PlanMasked, PlanPlay, PlanQ, PlanResult, PlanValue,  # noqa: F401
+                      STATUS_NAMES)
 from .obs_compact import CompactObs, record_cells  # noqa: F401
 from .env_state import EnvState  # noqa: F401
-from .search import (ExpertData, LookaheadResult, exhaustive_lookahead, expert_data, expert_labels,  # noqa: F401
-                     expert_rollout, follow_field, play_table, q_values)
+from .search import (ExpertData, LookaheadResult, PlanAblation, ablation_masks, exhaustive_lookahead,  # noqa: F401
+                     expert_data, expert_labels, expert_rollout, follow_field, play_table, q_values)

@@ -585,3 +585,82 @@ def expert_rollout(env, gamma: float = 1.0, horizon: Optional[int] = None, noise
     if records0 is None:
         records0 = env.pack_obs(env.obs)
     return expert_data(play, records0, pv.grid, env.rows, env.cols, env.config.vault_pos)
+
+
+# -- emitter ablation (heist_plan_masked, HeistEnv.plan_masked / plan_ablate) -------------------
+
+def ablation_masks(n_cams, n_guards, max_cams: int, max_guards: int) -> torch.Tensor:
+    """The leave-one-out emitter masks of heist_plan_masked as int64 [N, 1 + n_slot], n_slot =
+    max_cams + max_guards: variant 0 has the bit of every filled slot set (camera j < n_cams[e] is
+    slot j, guard g < n_guards[e] is slot max_cams + g), variant 1 + j is variant 0 without slot
+    j's bit -- equal to variant 0 where the env does not fill slot j.  Slot 63 is the int64's sign
+    bit (the kernel reads the word as uint64).  Pure torch, on the device of n_cams."""
+    n_cams = torch.as_tensor(n_cams).reshape(-1).to(torch.int64)
+    n_guards = torch.as_tensor(n_guards, device=n_cams.device).reshape(-1).to(torch.int64)
+    n_slot = int(max_cams) + int(max_guards)
+    if max_cams < 0 or max_guards < 0 or not 1 <= n_slot <= 64:
+        raise ValueError("ablation_masks: need 1 <= max_cams + max_guards <= 64")
+    j = torch.arange(n_slot, dtype=torch.int64, device=n_cams.device).reshape(1, n_slot)
+    filled = torch.where(j < max_cams, j < n_cams.reshape(-1, 1), j - max_cams < n_guards.reshape(-1, 1))
+    bit = torch.ones_like(j) << j                                  # [1, n_slot]; 1 << 63 wraps to the sign bit
+    own = torch.where(filled, bit, torch.zeros_like(bit))          # [N, n_slot], disjoint bits
+    full = own.sum(1, keepdim=True)                                # their OR (two's complement: exact)
+    return torch.cat([full, full - own], 1)
+
+
+@dataclass
+class PlanAblation:
+    """HeistEnv.plan_ablate's output: what every emitter of every layout costs the Solver, from the
+    leave-one-out variants of heist_plan_masked (variant 0: the layout as built; variant 1 + j: slot
+    j switched off; slots as in ablation_masks).  Tensors on the tables' device:
+    ticks [N, 1 + n_slot] int16, value [N, 1 + n_slot] float64 -- PlanMasked.ticks / value;
+    filled [N, n_slot] bool -- the env fills slot j;
+    ticks_saved [N, n_slot] int16 -- ticks[:, :1] - ticks[:, 1:] where both are solvable, else 0;
+    credit [N, n_slot] float64 -- value[:, 1:] - value[:, :1], one subtraction: what the emitter
+        costs the Solver's optimal return; 0.0 for an unfilled slot.  Non-negative on every batch
+        measured, but nothing here assumes it: a detection ends the episode, so where playing on
+        is worth less than the detection's penalty, an emitter's removal can lower the value;
+    critical [N, n_slot] bool -- the full layout has no undetected way to the vault, the layout
+        without slot j has one;
+    redundant [N, n_slot] bool -- a filled slot without which neither the ticks nor the value's
+        bits change."""
+    ticks: torch.Tensor
+    value: torch.Tensor
+    filled: torch.Tensor
+    ticks_saved: torch.Tensor
+    credit: torch.Tensor
+    critical: torch.Tensor
+    redundant: torch.Tensor
+
+    @staticmethod
+    def from_tables(ticks: torch.Tensor, value: torch.Tensor, filled: torch.Tensor) -> "PlanAblation":
+        """The derived fields from the leave-one-out tables.  Pure torch."""
+        n_slot = filled.shape[1]
+        if ticks.shape != (filled.shape[0], 1 + n_slot) or value.shape != ticks.shape:
+            raise ValueError("PlanAblation: ticks and value must be [N, 1 + n_slot] for filled [N, n_slot]")
+        filled = filled.bool()
+        t0, t1 = ticks[:, :1], ticks[:, 1:]
+        v0, v1 = value[:, :1].contiguous(), value[:, 1:].contiguous()
+        both = (t0 > 0) & (t1 > 0)
+        saved = torch.where(both, t0 - t1, torch.zeros_like(t1))
+        same = (t1 == t0) & (v1.view(torch.int64) == v0.view(torch.int64))
+        return PlanAblation(ticks, value, filled, saved, v1 - v0, filled & (t0 < 0) & (t1 > 0), filled & same)
+
+    def metrics(self, max_cams: int) -> dict:
+        """The trainer's four figures for this batch (AdversarialTrainer(track_emitter_credit=True)):
+        critical_layout_frac -- the share of the unsolvable layouts that one emitter's removal makes
+        solvable; redundant_emitter_frac -- the share of the filled emitters that are redundant;
+        camera_credit_mean / guard_credit_mean -- the mean credit over the filled cameras / guards
+        (slots below / from max_cams).  A share or a mean over nothing is 0.0."""
+        f = self.filled
+        unsolv = self.ticks[:, 0] < 0
+        cam = torch.zeros_like(f)
+        cam[:, :max_cams] = True
+        z = torch.zeros_like(self.credit)
+        s = torch.stack([unsolv.sum().double(), (unsolv & self.critical.any(1)).sum().double(),
+                         f.sum().double(), self.redundant.sum().double(),
+                         (f & cam).sum().double(), torch.where(f & cam, self.credit, z).sum(),
+                         (f & ~cam).sum().double(), torch.where(f & ~cam, self.credit, z).sum()]).cpu().tolist()
+        div = lambda a, b: a / b if b else 0.0  # noqa: E731
+        return {"critical_layout_frac": div(s[1], s[0]), "redundant_emitter_frac": div(s[3], s[2]),
+                "camera_credit_mean": div(s[5], s[4]), "guard_credit_mean": div(s[7], s[6])}

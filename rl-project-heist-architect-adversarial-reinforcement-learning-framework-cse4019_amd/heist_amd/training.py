@@ -159,7 +159,8 @@ class AdversarialTrainer:  # training.py:115-790
                  seed: Optional[int] = None, update_precision: str = "fp32", rollout_precision: str = "fp32",
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
                  solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
-                 track_optimal: bool = False, track_optimal_return: bool = False):
+                 track_optimal: bool = False, track_optimal_return: bool = False,
+                 track_emitter_credit: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -212,6 +213,15 @@ class AdversarialTrainer:  # training.py:115-790
         # cameras.  False: no launch, no metric, logs and checkpoints byte-identical
         self.track_optimal_return = bool(track_optimal_return)
         self._optimal_return = None  # optimal_return_mean of the latest valued layout batch
+        # True: every layout batch's emitters are switched off one at a time (HeistEnv.plan_ablate at
+        # gamma 1, one launch right after its set_layout + reset) and train_iteration reports the
+        # latest batch's critical_layout_frac (the share of its unsolvable layouts that one emitter's
+        # removal makes solvable), redundant_emitter_frac (the share of its filled emitters whose
+        # removal changes neither the fewest ticks nor the optimal return) and camera_credit_mean /
+        # guard_credit_mean (the mean optimal return a camera / a guard costs the Solver).  False: no
+        # launch, no metric, logs and checkpoints byte-identical
+        self.track_emitter_credit = bool(track_emitter_credit)
+        self._emitter_credit = None  # the four metrics of the latest ablated layout batch
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -347,6 +357,8 @@ class AdversarialTrainer:  # training.py:115-790
                     self._plan_layout_batch(good)
                 if self.track_optimal_return:
                     self._value_layout_batch(good)
+                if self.track_emitter_credit:
+                    self._ablate_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
@@ -365,6 +377,13 @@ class AdversarialTrainer:  # training.py:115-790
         sr, sc = self.config.start_pos
         v = self.env.plan_value(gamma=1.0).value[torch.as_tensor(env_ids, device=self.device), sr, sc]
         self._optimal_return = float(v.mean())
+
+    def _ablate_layout_batch(self, env_ids):
+        """The emitter credit of the layouts just set on env_ids (fresh after reset)."""
+        from .search import PlanAblation
+        ab = self.env.plan_ablate(gamma=1.0)
+        i = torch.as_tensor(env_ids, device=self.device)
+        self._emitter_credit = PlanAblation.from_tables(ab.ticks[i], ab.value[i], ab.filled[i]).metrics(self.env.max_cams)
 
     # -- rollout / scoring ------------------------------------------------------------------
     @torch.no_grad()
@@ -704,6 +723,8 @@ class AdversarialTrainer:  # training.py:115-790
             out["solvable_frac"], out["optimal_ticks_mean"] = self._optimal
         if self.track_optimal_return and self._optimal_return is not None:
             out["optimal_return_mean"] = self._optimal_return
+        if self.track_emitter_credit and self._emitter_credit is not None:
+            out.update(self._emitter_credit)
         return out
 
     # -- supervised pre-training on exact labels (no reference counterpart) -------------------

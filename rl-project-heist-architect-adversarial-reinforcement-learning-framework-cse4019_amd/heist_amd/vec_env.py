@@ -183,6 +183,40 @@ class PlanValue:
 
 
 @dataclass
+class PlanMasked:
+    """HeistEnv.plan_masked's output (heist_plan_masked, include/heist.h), device tensors; variant
+    (e, m) is env e planned with the emitter slots of masks[e, m] alone:
+    ticks [N, M] int16 -- the fewest ticks to a clean vault arrival from the Solver's cell (-1: none);
+    value [N, M] float64, action [N, M] int8 -- the largest discounted return from there and the
+        lowest action that starts it (PlanValue's at that cell);
+    vis [H, N, M, W] int32 -- row k - 1: the variant's visibility plane of the k-th tick from now;
+    togo_cells [N, M, R, C] int16, value_cells [N, M, R, C] float64 or None -- the whole tables
+        (PlanField.togo / PlanValue.value of the variant); with cells=True only;
+    masks [N, M] int64 -- the masks as given (bit j: slot j is live; slot 63 is the sign bit);
+    tick [N] int32 -- each env's tick at the call, -1 where it was done (PlanValue.tick)."""
+    ticks: torch.Tensor
+    value: torch.Tensor
+    action: torch.Tensor
+    vis: torch.Tensor
+    togo_cells: Optional[torch.Tensor]
+    value_cells: Optional[torch.Tensor]
+    masks: torch.Tensor
+    tick: torch.Tensor
+    rows: int
+    cols: int
+    gamma: float = 1.0
+
+    def vis_mask(self, k: int, m: int = 0) -> torch.Tensor:
+        """vis_k of variant m for k = 1 .. H as bool [N, R, C]."""
+        if not 1 <= k <= self.vis.shape[0]:
+            raise IndexError("vis_mask: k must be 1 .. %d" % self.vis.shape[0])
+        w = self.vis[k - 1, :, m]
+        sh = torch.arange(32, device=w.device, dtype=torch.int32)
+        bits = (w.unsqueeze(-1) >> sh) & 1
+        return bits.reshape(w.shape[0], -1)[:, :self.rows * self.cols].reshape(-1, self.rows, self.cols).bool()
+
+
+@dataclass
 class PlanQ:
     """HeistEnv.plan_q's output (heist_plan_q, include/heist.h; heist_amd.search.q_values gives the
     same on any device): the exact action values of visited states, [K, N] time-major, state
@@ -543,6 +577,63 @@ class HeistEnv:
         tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
         return PlanValue(value, action, vis, vticks, aticks, R, C, tuple(int(v) for v in self.config.vault_pos),
                          float(gamma), ex["grid"], tick)
+
+    # -- planner what-if (heist_plan_masked) --------------------------------------------------
+    @property
+    def plan_masked_supported(self) -> int:
+        """heist_plan_masked_supported: 1 when plan_masked() has a kernel for this handle (where
+        plan_value() has one: every grid up to 32 x 32; 0 at 64 x 64)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_masked_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_masked_supported")
+        return d
+
+    def plan_masked(self, masks, horizon: Optional[int] = None, gamma: float = 1.0, cells: bool = False) -> "PlanMasked":
+        """heist_plan_masked: every env as it stands planned under M sets of its emitters in one
+        launch -- the fewest ticks to the vault and the largest discounted return from the Solver's
+        cell with the emitter slots of masks[e, m] alone (bit j: slot j is live; cameras are slots
+        0 .. max_cams - 1, guard g is slot max_cams + g; bits of unfilled slots are ignored), plus
+        every variant's visibility planes and, with cells, the whole tables.  masks: int64 [N, M],
+        or [M] for the same masks on every env.  horizon and gamma as in plan_value.  vis takes
+        4 H N M W bytes.  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        mk = torch.as_tensor(masks)
+        if mk.dtype != torch.int64 or mk.dim() not in (1, 2) or (mk.dim() == 2 and mk.shape[0] != n):
+            raise ValueError("plan_masked: masks must be an int64 [%d, M] or [M] tensor" % n)
+        if mk.dim() == 1:
+            mk = mk.reshape(1, -1).expand(n, -1)
+        mk = mk.to(self.device).contiguous()
+        M = int(mk.shape[1])
+        kw = dict(device=self.device)
+        ticks = torch.empty((n, M), dtype=torch.int16, **kw)
+        value = torch.empty((n, M), dtype=torch.float64, **kw)
+        action = torch.empty((n, M), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, M, record_words(R, C)), dtype=torch.int32, **kw)
+        tcells = torch.empty((n, M, R, C), dtype=torch.int16, **kw) if cells else None
+        vcells = torch.empty((n, M, R, C), dtype=torch.float64, **kw) if cells else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_masked(self._h, H, float(gamma), M, nat.ptr(mk) if M else None, nat.ptr(ticks),
+                                                  nat.ptr(value), nat.ptr(action), nat.ptr(vis), nat.ptr(tcells),
+                                                  nat.ptr(vcells), self._stream()), "heist_plan_masked")
+        ex = self.export()
+        tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
+        return PlanMasked(ticks, value, action, vis, tcells, vcells, mk, tick, R, C, float(gamma))
+
+    def plan_ablate(self, horizon: Optional[int] = None, gamma: float = 1.0):
+        """Every env's emitters switched off one at a time: plan_masked with
+        heist_amd.search.ablation_masks of the envs' own emitter counts, as a
+        heist_amd.search.PlanAblation -- ticks and value of the layout as built (column 0) and
+        without slot j (column 1 + j), the ticks each emitter costs, its credit in return, and
+        which emitters are critical or redundant.  One launch; reads the envs only."""
+        from .search import PlanAblation, ablation_masks
+        ex = self.export()
+        mc, mg = self.max_cams, self.max_guards
+        pm = self.plan_masked(ablation_masks(ex["n_cams"], ex["n_guards"], mc, mg), horizon=horizon, gamma=gamma)
+        j = torch.arange(mc + mg, device=self.device).reshape(1, -1)
+        filled = torch.where(j < mc, j < ex["n_cams"].reshape(-1, 1), j - mc < ex["n_guards"].reshape(-1, 1))
+        return PlanAblation.from_tables(pm.ticks, pm.value, filled)
 
     # -- planner Q (heist_plan_q) --------------------------------------------------------------
     PLAN_Q_OUTPUTS = ("q", "value", "best", "optimal", "gap")

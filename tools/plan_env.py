@@ -32,6 +32,13 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # search.q_values on the same device tensors and the
                                                  # plan_value(all_ticks=True) launch that makes its inputs; also
                                                  # written to profiles/plan_q.log
+  python tools/plan_env.py --ablate [--gamma G]   # the planner what-if (heist_plan_masked, HeistEnv.plan_ablate) on the
+                                                 # three batches: every emitter switched off in turn, M = 1 + n_slot
+                                                 # variants per env in one launch -- the histograms of critical and
+                                                 # redundant emitters per layout, the share of unsolvable layouts with
+                                                 # and without a critical emitter, and the launch next to the route it
+                                                 # replaces, M x (heist_plan_field + heist_plan_value); also written to
+                                                 # profiles/plan_masked.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -349,6 +356,63 @@ def q_mode(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def ablate_table(args, dev):
+    """heist_plan_masked's leave-one-out launch next to M x (heist_plan_field + heist_plan_value), the
+    existing route without its set_layout / reset, same handle, same process, same state (all of
+    them only read the envs): one JSON line per batch."""
+    from heist_amd.search import ablation_masks
+    H = min(args.horizon or args.max_steps, 1024)
+    N = args.envs
+    lines = []
+    for kind in ("architect", "empty", "synthetic"):
+        env = make_env(args, kind, dev)
+        kc = env.kernel_config()
+        assert env.plan_masked_supported == 1, kc
+        ab = env.plan_ablate(H, gamma=args.gamma)
+        M = ab.ticks.shape[1]
+        unsolv = ab.ticks[:, 0] < 0
+        n_unsolv, n_filled = int(unsolv.sum()), int(ab.filled.sum())
+        with_crit = int((unsolv & ab.critical.any(1)).sum())
+
+        def hist(per_env):
+            return {str(k): int((per_env == k).sum()) for k in range(int(per_env.max()) + 1)}
+
+        mc = env.max_cams
+        f = ab.filled
+        out = {"config": "%dx%d" % (args.grid, args.grid), "envs": N, "layouts": kind, "horizon": H, "gamma": args.gamma,
+               "multi_waves": kc["multi_waves"], "variants_per_env": M, "filled_emitters": n_filled,
+               "solvable_frac": float((~unsolv).float().mean()), "unsolvable_layouts": n_unsolv,
+               "unsolvable_with_a_critical_emitter_frac": with_crit / n_unsolv if n_unsolv else None,
+               "unsolvable_jointly_blocked_frac": (n_unsolv - with_crit) / n_unsolv if n_unsolv else None,
+               "redundant_emitter_frac": int(ab.redundant.sum()) / n_filled if n_filled else None,
+               "critical_emitters_per_layout": hist(ab.critical.sum(1)),
+               "redundant_emitters_per_layout": hist(ab.redundant.sum(1)),
+               "camera_credit_mean": float(ab.credit[:, :mc][f[:, :mc]].mean()) if bool(f[:, :mc].any()) else None,
+               "guard_credit_mean": float(ab.credit[:, mc:][f[:, mc:]].mean()) if bool(f[:, mc:].any()) else None,
+               "credit_min": float(ab.credit.min()),
+               "ticks_saved_mean_where_both_solvable":
+                   float(ab.ticks_saved[f & (ab.ticks[:, :1] > 0)].float().mean()) if bool((f & (ab.ticks[:, :1] > 0)).any()) else None}
+        del ab
+        x = env.export()
+        masks = ablation_masks(x["n_cams"], x["n_guards"], env.max_cams, env.max_guards)
+        ms = timed(dev, lambda: env.plan_masked(masks, H, gamma=args.gamma), args.warmup, args.runs)
+        m = statistics.median(ms)
+        ys = timed(dev, lambda: (env.plan_field(H), env.plan_value(H, gamma=args.gamma)), args.warmup, args.runs)
+        y = statistics.median(ys) * M
+        out["masked"] = {"launch_ms_median": m, "launch_ms": ms, "ns_per_variant_tick": m * 1e6 / (H * N * M)}
+        out["yardstick_M_x_field_plus_value"] = {"ms": y, "field_plus_value_ms_median": statistics.median(ys),
+                                                 "field_plus_value_ms": ys}
+        out["masked_over_yardstick"] = m / y
+        env.close()
+        lines.append(json.dumps(out))
+        print(lines[-1], flush=True)
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_masked.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --ablate --gamma %r\n" % args.gamma)
+        fh.write("\n".join(lines) + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -369,17 +433,21 @@ def main(argv=None):
                     "togo_ticks / value_ticks and action_ticks")
     ap.add_argument("--value", action="store_true", help="time heist_plan_value next to heist_plan_field on all three "
                     "batches, with the start cell's values and the length of the return-optimal episodes")
-    ap.add_argument("--gamma", type=float, default=1.0, help="with --value: the discount")
+    ap.add_argument("--gamma", type=float, default=1.0, help="with --value / --ablate: the discount")
     ap.add_argument("--play", action="store_true", help="time heist_plan_play next to the Python path it replaces and "
                     "to heist_plan_value on the --layouts batch")
     ap.add_argument("--noise", type=float, default=0.1, help="with --play / --q: the noisy play's probability")
     ap.add_argument("--q", action="store_true", help="time heist_plan_q next to search.q_values on the same device "
                     "tensors and to the plan_value(all_ticks=True) launch that feeds it, on all three batches")
+    ap.add_argument("--ablate", action="store_true", help="time heist_plan_masked's leave-one-out launch next to "
+                    "M x (heist_plan_field + heist_plan_value) on all three batches, with the critical / redundant emitters")
     ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
-                    "profiles/plan_play.log, --q's: profiles/plan_q.log)")
+                    "profiles/plan_play.log, --q's: profiles/plan_q.log, --ablate's: profiles/plan_masked.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.ablate:
+        return ablate_table(args, dev)
     if args.q:
         return q_mode(args, dev)
     if args.play:

@@ -1,7 +1,8 @@
 #!/bin/bash
 # Register / occupancy / spill report of the env kernels (cross-compiled for gfx950, no GPU).
 # usage: tools/regs.sh [regex]   (default: step|reset|cones; `plan` the planner's and the planner
-#        field's instances, `field` plan_field_kernel's alone, `value` plan_value_kernel's alone)
+#        field's instances, `field` plan_field_kernel's alone, `value` plan_value_kernel's alone,
+#        `masked` plan_masked_kernel's alone)
 #        tools/regs.sh play      plan_play_kernel (heist_play.hip), with its SGPRs and LDS
 #        tools/regs.sh q         plan_q_kernel (heist_q.hip), the same columns
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
