@@ -405,6 +405,81 @@ int heist_plan_masked(heist_t h, int horizon, double gamma, int M, const uint64_
                       int16_t* ticks_out, double* value_out, int8_t* action_out, uint32_t* vis_out,
                       int16_t* togo_cells_out, double* value_cells_out, heist_stream_t stream);
 
+/* Planner placement, no reference counterpart: heist_plan_masked's two answers for every env with
+ * one more camera in it -- M candidate cameras per env in one launch, which is what tells where a
+ * camera the layout does not have would have mattered, and how much.  Visibility is a union over the
+ * emitters, an emitter blocks neither a ray nor a move (only wall tiles do), and a camera is only
+ * ever placed on an EMPTY tile (environment.py:124-135, :160-167), so it never changes the wall
+ * plane: the visibility of "this layout plus camera X" on a tick is the layout's own row OR X's cone
+ * on that tick.  The launch therefore casts the candidate alone, against the env's wall plane, and
+ * takes the layout's share as given rows; none of the env's own emitters is read or cast.
+ *   cand     [N][M][6] float64, 8-byte aligned, M >= 1: cand[e][m] is a heist_set_layout cam_params
+ *            row (row, col, fov_angle, heading, rotation_speed, vision_range) and becomes a camera
+ *            record by heist_set_layout's own conversion of an accepted camera: tile ((int)row,
+ *            (int)col), range (int)vision_range, max(int(fov_angle * 2), 30) rays.  heading is the
+ *            camera's heading now, at env e's current tick: planned tick k = 1 .. HK first rotates
+ *            it, heading = (heading + rotation_speed * 1.0) mod 360 (Python's %, once per tick,
+ *            accumulated as the env's cameras accumulate it), and then casts, as an env camera does.
+ *   base_vis [horizon][N][W] uint32, W = heist_obs_record_bytes(rows, cols) / 4, 16-byte aligned:
+ *            row (k-1, e) holds the visibility on tick k that the candidates are added to, in the
+ *            record's bit order -- heist_plan_field's, heist_plan_value's or (M = 1) heist_plan_masked's
+ *            vis_out of the same handle state.  It is trusted as given: its words 0 .. ceil(R C /
+ *            32) - 1 of the rows k <= HK are used as they are, nothing else of it is read.  With
+ *            heist_plan_field's rows the result is "the layout plus X"; with the rows of a
+ *            heist_plan_masked variant that switches slot j off it is "the layout without slot j,
+ *            plus X", a relocation.  base_vis and vis_out must not overlap.
+ * Candidate (e, m) is valid iff both hold:
+ *   1. it is placeable in env e's grid as it stands (environment.py:160-167): with r = (int)row, c =
+ *      (int)col, 0 < r < R-1, 0 < c < C-1 and tile (r, c) is EMPTY -- not a wall, the start, the
+ *      vault, a camera or a guard's start tile.  One divergence from a layout rebuilt with the
+ *      candidate in its camera list: heist_set_layout places cameras before guards, so there a
+ *      camera on a guard's start tile is accepted (the guard then takes the tile over); here it is
+ *      not.  The budget and the camera slots are ignored, as if 3 points and a free slot were there;
+ *   2. its parameters are ones the raycaster takes, every comparison false for a NaN:
+ *        |row| < 2^31 and |col| < 2^31      (the (int) conversions are defined)
+ *        0 < fov_angle <= 16000             (the ray count stops growing there; it fits the int16)
+ *        |heading| <= 1e300, |rotation_speed| <= 1e300   (their sum is finite; every rotated
+ *                                            heading then lies in [0, 360])
+ *        0 <= vision_range < 32768          (the record's int16 range)
+ *      No float64 bit pattern in cand makes the launch read or write out of bounds: a candidate
+ *      that fails 2. is never converted and never cast.
+ *   valid_out [N][M] uint8: 1 for a valid candidate, else 0 (whatever HK is).
+ * Variant (e, m) is planned from env e's current state as heist_plan_masked plans one, HK =
+ * min(horizon, max_steps - tick[e]) ticks (0 for an env already done), over
+ *   vis_k(e, m) = base_vis[k-1][e] | cone_k(e, m),   k = 1 .. HK,
+ * cone_k the tiles the candidate's rays mark on tick k: cast with the handle's ray_mode on the path
+ * an env camera takes (fp32 fast path, tie buckets, exact recast of near-tie rays; exact-only above
+ * range 6), the camera's own tile never marked by its own rays.  A camera of range 0 has no sample
+ * and an empty cone (security.py:76-82), and so has an invalid candidate: such a variant is the
+ * base rows' plan.
+ *   ticks_out, value_out, action_out, togo_cells_out, value_cells_out: heist_plan_masked's outputs
+ *            of the same names, shapes and alignments over those vis_k -- togo_0 and V_0 by
+ *            heist_plan_field's and heist_plan_value's recurrences, V_0 in heist_plan_value's own
+ *            arithmetic (the same lines in the same order, each one IEEE double operation, none
+ *            contracted, the first maximum under a strict greater-than).
+ *   vis_out  [horizon][N][M][W] uint32, 16-byte aligned, required (it is the backward sweeps'
+ *            history): row (k-1, e, m), at (((k-1) N + e) M + m) W words, holds vis_k(e, m); the pad
+ *            words are 0 and rows k > HK are 0, as in heist_plan_masked.
+ * Every variant of an env with HK = 0 holds -1 / 0.0 / -1, in the cell tables too.
+ * With heist_plan_field's rows as base_vis, a valid candidate's variant (range >= 1) is
+ * heist_plan_field / heist_plan_value, bit for bit, on a handle built from the same layout with the
+ * candidate appended to its camera list (budget + 3, one more camera slot) and brought to the same
+ * state.
+ * The launch only reads the env, as heist_plan_field does.
+ * heist_plan_place_supported: heist_plan_masked_supported's value (the kernel's LDS is
+ *   heist_plan_masked's): every grid up to 32 x 32 at 1, 2 and 4 K-tick waves; 64 x 64 is not
+ *   supported.  -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, gamma not finite or outside [0, 1], M < 1 or N M >= 2^31,
+ * a NULL cand, base_vis, valid_out, ticks_out, value_out, action_out or vis_out, base_vis or vis_out
+ * not 16-byte aligned, cand, value_out or value_cells_out not 8-byte aligned, ticks_out or
+ * togo_cells_out not 2-byte aligned, a probe mode armed (HEIST_PROBE_MODE),
+ * heist_plan_place_supported 0. */
+int heist_plan_place_supported(heist_t h);
+int heist_plan_place(heist_t h, int horizon, double gamma, int M, const double* cand,
+                     const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
+                     int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                     double* value_cells_out, heist_stream_t stream);
+
 /* Planner playout, no reference counterpart: one episode per env played from a planner's per-tick
  * tables -- the table's own (expert) play, or that play perturbed on a counter-hashed share of the
  * steps, every visited state still labelled by the table.  The emitters do not depend on the

@@ -887,6 +887,17 @@ __device__ __forceinline__ Emit cam_emit(const Cam& cm) {
   return E;
 }
 
+// The record of an accepted camera from its heist_set_layout cam_params row (row, col, fov_angle,
+// heading, rotation_speed, vision_range) on tile (r, c) = ((int)cp[0], (int)cp[1]): set_layout_kernel's
+// conversion, which heist_plan_place's candidates share.
+__device__ __forceinline__ Cam cam_record(const double* cp, int r, int c) {
+  Cam cm;
+  cm.fov = cp[2]; cm.heading = cp[3]; cm.speed = cp[4];
+  cm.row = (int16_t)r; cm.col = (int16_t)c; cm.range = (int16_t)cp[5];
+  cm.num_rays = (int16_t)num_rays_for(cm.fov);
+  return cm;
+}
+
 __device__ __forceinline__ Emit guard_emit(const Guard& gd) {
   Emit E;
   E.hmh = gd.heading - gd.fov / 2.0;
@@ -3266,6 +3277,297 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ
 }
 
 // ---------------------------------------------------------------------------
+// Planner placement (heist_plan_place): ticks and return with one more camera
+// ---------------------------------------------------------------------------
+//
+// plan_masked_kernel's question for M variants of every env, variant (e, m) being the env plus the
+// candidate camera cand[e][m] (include/heist.h).  Visibility is a union over emitters, an emitter
+// blocks neither rays nor moves, and a camera only ever stands on an EMPTY tile, so it leaves the
+// wall plane alone: the variant's vis_k is the caller's base row k OR the candidate's cone on tick
+// k.  The env's own emitters are therefore never loaded and never cast -- the emitter table holds
+// one slot, the candidate's, whose record lives in wave 0's registers and rotates as an env camera does --
+// and the forward pass costs one camera per tick whatever the layout holds.  One workgroup per
+// (env, variant), block b = order entry b / M, variant b % M, as plan_masked_kernel.
+// Forward pass: rotate, cam_emit, publish_emitters (one slot), clear_planes, cast_rays (DEDUP, tie
+// buckets: the call an env camera gets), then the plane packed 64 cells per ballot into the free
+// visibility-row words of LDS; after the barrier that closes the plane's readers lane t ORs word t
+// with the base row's word t -- loaded one tick ahead, so the load lands during the cast -- and
+// stores it to the variant's row of vis_out.  An invalid candidate, and a valid one of range 0
+// (block-uniform), casts nothing and copies the base rows.
+// Backward passes: plan_masked_kernel's two sweeps (a copy: each planner's instances keep their
+// registers), the LDS is plan_value_lds.
+
+// A candidate's parameters are ones the raycaster can take (include/heist.h): written so that a NaN
+// fails every test.  |row|, |col| < 2^31 makes the (int) casts defined; fov <= 16000 is where
+// num_rays_for stops growing (and keeps every ray angle within fast_dir's and heist_trig's
+// reductions); heading and speed bounded so that their sum is finite (py_mod360 then brings every
+// later heading into [0, 360]); the range fits the record's int16.
+__device__ __forceinline__ bool cam_params_castable(const double* cp) {
+  return __builtin_fabs(cp[0]) < 2147483648.0 && __builtin_fabs(cp[1]) < 2147483648.0 && cp[2] > 0.0 &&
+         cp[2] <= 16000.0 && __builtin_fabs(cp[3]) <= 1e300 && __builtin_fabs(cp[4]) <= 1e300 && cp[5] >= 0.0 &&
+         cp[5] < 32768.0;
+}
+
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_place_kernel(
+    EnvParams p, int H, double gamma, int M, const double* __restrict__ cand, const uint32_t* __restrict__ base_vis,
+    uint8_t* __restrict__ valid_out, int16_t* __restrict__ ticks_out, double* __restrict__ value_out,
+    int8_t* __restrict__ action_out, uint32_t* vis_out, int16_t* __restrict__ togo_cells_out,
+    double* __restrict__ value_cells_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr uint32_t kNone = 0xFFFFu;
+  const int oi = uni((int)(blockIdx.x / (uint32_t)M)), var = uni((int)blockIdx.x - oi * M);
+  const int e = p.dispatch_order ? (p.order[oi] & kOrderEnvMask) : oi;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, C = p.C;
+  const size_t NM = (size_t)p.n_envs * (size_t)M, em = (size_t)e * (size_t)M + (size_t)var;  // rows per tick, this row
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  // plan_masked_kernel's carve-up (plan_value_lds); the record array is not used
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // the guard plane: cleared, never stamped
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6;
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;  // the record's words (obs_record_words)
+  double* val = reinterpret_cast<double*>(uq + 128 * W);           // [2][RC] values, tick parity (16-byte aligned)
+  uint16_t* togo = reinterpret_cast<uint16_t*>(val);               // [2][RC] ticks to go, over val's first array
+  uint32_t* vrow = reinterpret_cast<uint32_t*>(val + 2 * RC);      // [2][nvis] visibility rows, tick parity
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;  // not used: the env's own emitters are not cast, and their loads fall away
+    prefetch<NT>(p, e, eb, L, raw);
+  }
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  // the candidate's row, the same six doubles in every lane
+  const double* cp = cand + em * 6;
+  const bool castable = cam_params_castable(cp);
+  const int cr = castable ? (int)cp[0] : 0, cc = castable ? (int)cp[1] : 0;
+  const bool inside = castable && cr > 0 && cr < p.R - 1 && cc > 0 && cc < C - 1;  // environment.py:160-167
+  __syncthreads();  // grid and stop map in LDS
+  const bool valid = uni((int)(inside && L.grid[inside ? cr * C + cc : 0] == kEmpty)) != 0;
+  if (t == 0) valid_out[em] = valid ? 1 : 0;
+  // the candidate's record, in every lane's registers (wave-uniform); lane 0 rotates and casts its copy.  Not in
+  // the LDS record array: a handle without emitter slots has none
+  Cam cm{};
+  if (valid) cm = cam_record(cp, cr, cc);
+  // a range of 0 has no sample (security.py:76-82: no distance to walk): nothing is cast.  cast_rays is not asked:
+  // march_fast's clamped form repeats sample n_samp, and with n_samp = 0 that is the camera's own tile
+  const bool casts = valid && cm.range > 0;
+
+  // cell / C as a multiply-shift (plan_kernel)
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+  // word t of base row k (row k is the base's vis_{k+1}); nvis <= NT: launch_plan_place requires
+  // plan_value_variant_exists, which holds only where ceil(R C / 32) <= 64 W
+  auto base_word = [&](int k) -> uint32_t {
+    return t < nvis ? base_vis[((size_t)k * (size_t)p.n_envs + (size_t)e) * WR + t] : 0u;
+  };
+
+  // ---- forward: vis_1 .. vis_HK into the variant's rows of vis_out
+  if (casts) {
+    uint32_t bw = HK > 0 ? base_word(0) : 0u;
+    for (int k = 1; k <= HK; ++k) {
+      // (the barrier that closed the previous tick's pack also closed its readers of vis / em)
+      if (w0) {
+        Emit E;
+        E.kind = -1;
+        cm.heading = py_mod360(cm.heading + cm.speed * 1.0);  // the camera rotates, then casts (security.py:49-51)
+        if (t == 0) E = cam_emit(cm);
+        publish_emitters(L, E, 1);
+      }
+      // the planner kernels' clear: it also zeroes the guard plane, which nothing stamps or reads here (a few
+      // 16-byte LDS stores per lane and tick; kept so that the tick is the one plan_masked_kernel runs)
+      clear_planes<NT>(p, L, gvis, true);
+      __syncthreads();  // emitter table, cleared plane
+      cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+      const uint32_t bnext = k < HK ? base_word(k) : 0u;  // lands during the next tick's cast
+      __syncthreads();  // plane complete
+
+      // the candidate's cone, 64 cells per ballot, as the two words of its chunk
+      uint32_t* cone = vrow + (k & 1) * nvis;
+      for (int ch = wave; ch < n_chunk; ch += W) {
+        const int cell = 64 * ch + lane;
+        bool seen = false;
+        if (cell < RC) {
+          const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+          seen = L.vis[L.at(r, c)] != 0;
+        }
+        const unsigned long long m = __ballot(seen);
+        if (lane < 2 && 2 * ch + lane < nvis) cone[2 * ch + lane] = (uint32_t)(m >> (32 * lane));
+      }
+      __syncthreads();  // the plane's readers are done; the cone's words complete
+      // (the next writer of this parity's words is two ticks on, behind two more barriers)
+      uint32_t* row = vis_out + ((size_t)(k - 1) * NM + em) * WR;
+      for (int i = t; i < WR; i += NT) row[i] = i < nvis ? (cone[i] | bw) : 0u;  // i < nvis: i == t; pad words 0
+      bw = bnext;
+    }
+  } else {
+    for (int k = 1; k <= HK; ++k) {
+      const uint32_t bw = base_word(k - 1);
+      uint32_t* row = vis_out + ((size_t)(k - 1) * NM + em) * WR;
+      for (int i = t; i < WR; i += NT) row[i] = i < nvis ? bw : 0u;
+    }
+  }
+
+  // the rows this variant did not run, 16 bytes per store (WR is a multiple of 4, vis_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - HK) * q4; i += NT) {
+      const int r = HK + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(vis_out + ((size_t)r * NM + em) * WR)[q] = z;
+    }
+  }
+  if (HK == 0) {  // block-uniform: an env already done (or past max_steps) has no plan and collects nothing
+    if (t == 0) {
+      ticks_out[em] = (int16_t)-1;
+      value_out[em] = 0.0;
+      action_out[em] = (int8_t)-1;
+    }
+    for (int x = t; x < RC; x += NT) {
+      if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)-1;
+      if (value_cells_out) value_cells_out[em * RC + x] = 0.0;
+    }
+    return;
+  }
+
+  // row k of vis_out is vis_{k+1}
+  auto load_row = [&](int k) {
+    return __hip_atomic_load(vis_out + ((size_t)k * NM + em) * WR + (t < nvis ? t : 0), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const int vr = p.vr, vc = p.vc, vcell = vr * C + vc;
+  const int pcell = uni(s.pos_r) * C + uni(s.pos_c);  // the Solver's cell
+
+  // ---- backward, ticks: togo_{HK-1} .. togo_0 (plan_masked_kernel's sweep)
+  __threadfence();  // this variant's rows visible to the lanes that read them back
+  __syncthreads();  // the forward pass's last readers of the visibility-row words are done
+  for (int x = t; x < RC; x += NT) togo[(HK & 1) * RC + x] = (uint16_t)kNone;  // togo_HK
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;          // vis_{k+1}
+    const uint16_t* nxt = togo + ((k + 1) & 1) * RC;     // togo_{k+1}
+    uint16_t* cur = togo + (k & 1) * RC;                 // togo_k
+    for (int x = t; x < RC; x += NT) {
+      uint32_t best = kNone;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        auto tg = [&](int y) -> uint32_t {
+          if ((vk[y >> 5] >> (y & 31)) & 1u) return kNone;
+          if (y == vcell) return 1u;
+          const uint32_t v = nxt[y];
+          return v == kNone ? kNone : v + 1u;
+        };
+        auto moved = [&](bool in_grid, int y) { return in_grid && L.grid[y] != kWall ? y : x; };
+        best = tg(x);
+        uint32_t v = tg(moved(r > 0, x - C));
+        if (v < best) best = v;
+        v = tg(moved(r + 1 < p.R, x + C));
+        if (v < best) best = v;
+        v = tg(moved(c > 0, x - 1));
+        if (v < best) best = v;
+        v = tg(moved(c + 1 < C, x + 1));
+        if (v < best) best = v;
+      }
+      cur[x] = (uint16_t)best;
+      if (k == 0) {
+        if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)(uint16_t)best;
+        if (x == pcell) ticks_out[em] = (int16_t)(uint16_t)best;
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // togo_k and vis_k complete; their previous holders' readers are done
+  }
+
+  // ---- backward, return: V_{HK-1} .. V_0 (plan_masked_kernel's sweep) over the same rows; the
+  // barrier above closed the last readers of togo and of both visibility rows
+  for (int x = t; x < RC; x += NT) val[(HK & 1) * RC + x] = 0.0;  // V_HK
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  const int D0 = uni(s.initial_dist);
+  const bool bonus = D0 > 3;
+  const double r_step = p.r_step, r_detect = p.r_detect, r_vault = p.r_vault;
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;        // vis_{k+1}
+    const double* nxt = val + ((k + 1) & 1) * RC;      // V_{k+1}
+    double* cur = val + (k & 1) * RC;                  // V_k
+    const bool last = tick0 + k + 1 >= p.max_steps;    // the env times out on this tick (k = HK - 1 only)
+    for (int x = t; x < RC; x += NT) {
+      double best = 0.0;
+      int act = -1;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        const int dx = iabs_(r - vr) + iabs_(c - vc);
+        // q of the move to cell y = (yr, yc): step_multi_body's reward in its order, then the tail
+        auto q = [&](int y, int yr, int yc) -> double {
+          const int curr = iabs_(yr - vr) + iabs_(yc - vc);
+          double rew = r_step;
+          rew += (double)(dx - curr) * 0.1;
+          if (curr <= 3 && bonus) rew += 0.05 * (double)(3 - curr);
+          const bool seen = ((vk[y >> 5] >> (y & 31)) & 1u) != 0u;
+          if (seen) rew += r_detect;
+          if (y == vcell) rew += r_vault;
+          if (last) {
+            double frac = 1.0 - (double)curr / (double)(D0 > 1 ? D0 : 1);
+            if (frac < 0.0) frac = 0.0;
+            rew += frac * 2.0;
+          }
+          const double on_ = rew + gamma * nxt[y];
+          return (seen || y == vcell || last) ? rew : on_;
+        };
+        best = q(x, r, c);
+        act = 0;
+        bool ok = r > 0 && L.grid[x - C] != kWall;
+        double v = ok ? q(x - C, r - 1, c) : best;
+        if (v > best) best = v, act = 1;
+        ok = r + 1 < p.R && L.grid[x + C] != kWall;
+        v = ok ? q(x + C, r + 1, c) : best;
+        if (v > best) best = v, act = 2;
+        ok = c > 0 && L.grid[x - 1] != kWall;
+        v = ok ? q(x - 1, r, c - 1) : best;
+        if (v > best) best = v, act = 3;
+        ok = c + 1 < C && L.grid[x + 1] != kWall;
+        v = ok ? q(x + 1, r, c + 1) : best;
+        if (v > best) best = v, act = 4;
+      }
+      cur[x] = best;
+      if (k == 0) {
+        if (value_cells_out) value_cells_out[em * RC + x] = best;
+        if (x == pcell) {
+          value_out[em] = best;
+          action_out[em] = (int8_t)act;
+        }
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // V_k and vis_k complete; their previous holders' readers are done
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean K-tick kernel (heist_step_multi, one wave per env, grids up to 20 x 20)
 // ---------------------------------------------------------------------------
 //
@@ -4270,11 +4572,7 @@ __global__ __launch_bounds__(64) void set_layout_kernel(EnvParams p, int max_wal
       const int r = (int)cp[0], c = (int)cp[1];
       if (placeable(r, c) && total - spent >= 3) {
         spent += 3;
-        Cam cm;
-        cm.fov = cp[2]; cm.heading = cp[3]; cm.speed = cp[4];
-        cm.row = (int16_t)r; cm.col = (int16_t)c; cm.range = (int16_t)cp[5];
-        cm.num_rays = (int16_t)num_rays_for(cm.fov);
-        p.cams[(size_t)e * p.max_cams + nc] = cm;
+        p.cams[(size_t)e * p.max_cams + nc] = cam_record(cp, r, c);
         g[r * C + c] = kCamera;
         ++nc;
       }
@@ -4962,6 +5260,27 @@ hipError_t launch_plan_masked(const EnvParams& p, int horizon, double gamma, int
   }
   HEIST_MULTI_VARIANTS(HEIST_MASKED_CASE)
 #undef HEIST_MASKED_CASE
+  return hipErrorInvalidValue;  // not reached
+}
+
+// heist_plan_place: heist_plan_masked's instances, LDS, support and grid of workgroups.
+hipError_t launch_plan_place(const EnvParams& p, int horizon, double gamma, int M, const double* cand,
+                             const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
+                             int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
+                             hipStream_t st) {
+  if (!plan_value_variant_exists(p) || M < 1 || (size_t)p.n_envs * (size_t)M > 0x7fffffffull)
+    return hipErrorInvalidValue;
+  const size_t lds = plan_value_lds(p);
+  const unsigned blocks = (unsigned)p.n_envs * (unsigned)M;
+#define HEIST_PLACE_CASE(W, D)                                                                                   \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                    \
+    hipLaunchKernelGGL((plan_place_kernel<W, D>), dim3(blocks), dim3(64 * W), lds, st, p, horizon, gamma, M,     \
+                       cand, base_vis, valid_out, ticks_out, value_out, action_out, vis_out, togo_cells_out,     \
+                       value_cells_out);                                                                         \
+    return hipGetLastError();                                                                                    \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_PLACE_CASE)
+#undef HEIST_PLACE_CASE
   return hipErrorInvalidValue;  // not reached
 }
 

@@ -7,9 +7,10 @@ hand-written HIP kernels for gfx950 behind the C ABI in include/heist.h
 __version__ = "0.1.0"
 
 from .environment import EnvironmentConfig, HeistEnvironment  # noqa: F401
-from .vec_env import (HeistEnv, LayoutBatch, PlanField, PlanMasked, PlanPlay, PlanQ, PlanResult, PlanValue,  # noqa: F401
-                      STATUS_NAMES)
+from .vec_env import (HeistEnv, LayoutBatch, PlanField, PlanMasked, PlanPlace, PlanPlay, PlanQ, PlanResult,  # noqa: F401
+                      PlanValue, STATUS_NAMES)
 from .obs_compact import CompactObs, record_cells  # noqa: F401
 from .env_state import EnvState  # noqa: F401
-from .search import (ExpertData, LookaheadResult, PlanAblation, ablation_masks, exhaustive_lookahead,  # noqa: F401
-                     expert_data, expert_labels, expert_rollout, follow_field, play_table, q_values)
+from .search import (ExpertData, LookaheadResult, PlacementScan, PlanAblation, RelocationScan, ablation_masks,  # noqa: F401
+                     camera_candidates, exhaustive_lookahead, expert_data, expert_labels, expert_rollout,
+                     follow_field, greedy_cameras, placement_scan, play_table, q_values, relocation_scan)

@@ -20,6 +20,11 @@ for SolverAgent.imitation_update.
 
 q_values restates heist_plan_q (HeistEnv.plan_q) in pure torch on any device: the five exact action
 values of visited states, their maximum, the set of optimal actions and the gap of the action taken.
+
+camera_candidates, placement_scan, relocation_scan and greedy_cameras ask the Architect's side of
+the question with heist_plan_place (HeistEnv.plan_place): what one more camera on any interior cell
+would cost the Solver, where else a camera the layout has could have stood, and the exact greedy
+adversary built camera by camera.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -664,3 +669,206 @@ class PlanAblation:
         div = lambda a, b: a / b if b else 0.0  # noqa: E731
         return {"critical_layout_frac": div(s[1], s[0]), "redundant_emitter_frac": div(s[3], s[2]),
                 "camera_credit_mean": div(s[5], s[4]), "guard_credit_mean": div(s[7], s[6])}
+
+
+# -- camera placement (heist_plan_place, HeistEnv.plan_place) -----------------------------------
+
+def camera_candidates(grid, headings, fov: float, speed: float, vision_range) -> torch.Tensor:
+    """One candidate camera per interior cell and heading, for every env of grid [N, R, C] int8
+    (HeistEnv.grid_snapshot() or a CPU tensor), as heist_plan_place's cand rows float64
+    [N, M, 6] = (row, col, fov, heading, speed, vision_range), M = (R - 2)(C - 2) len(headings):
+    cells in row-major order, headings innermost, candidate ((r - 1)(C - 2) + c - 1) len(headings) +
+    h stands on (r, c) with headings[h].  Every interior cell is listed whatever stands on it --
+    the kernel's `valid` says which are placeable -- so M and the order are the same for every
+    env.  Pure torch, on the device of grid."""
+    grid = torch.as_tensor(grid)
+    if grid.dim() != 3 or grid.shape[1] < 3 or grid.shape[2] < 3:
+        raise ValueError("camera_candidates: grid must be [N, R, C] with R, C >= 3")
+    n, R, C = (int(v) for v in grid.shape)
+    dev = grid.device
+    hd = torch.as_tensor(headings, dtype=torch.float64, device=dev).reshape(-1)
+    nh = int(hd.numel())
+    if nh < 1:
+        raise ValueError("camera_candidates: need at least one heading")
+    r = torch.arange(1, R - 1, dtype=torch.float64, device=dev).reshape(-1, 1, 1).expand(R - 2, C - 2, nh)
+    c = torch.arange(1, C - 1, dtype=torch.float64, device=dev).reshape(1, -1, 1).expand(R - 2, C - 2, nh)
+    h = hd.reshape(1, 1, nh).expand(R - 2, C - 2, nh)
+    one = torch.ones_like(r)
+    rows = torch.stack([r, c, one * float(fov), h, one * float(speed), one * float(vision_range)], -1)
+    return rows.reshape(1, -1, 6).expand(n, -1, -1).contiguous()
+
+
+@dataclass
+class PlacementScan:
+    """placement_scan's output: what every candidate camera would do to every env, without the
+    visibility rows.  Tensors on the tables' device:
+    valid [N, M] bool, ticks [N, M] int16, value [N, M] float64, action [N, M] int8 -- PlanPlace's;
+    ticks0 [N] int16, value0 [N] float64 -- the baseline: the plan of the base rows alone;
+    cands [N, M, 6] float64 -- the candidates as given."""
+    valid: torch.Tensor
+    ticks: torch.Tensor
+    value: torch.Tensor
+    action: torch.Tensor
+    ticks0: torch.Tensor
+    value0: torch.Tensor
+    cands: Optional[torch.Tensor] = None
+
+    def eligible(self) -> torch.Tensor:
+        """[N, M] bool: the valid candidates that leave an undetected way to the vault (ticks >= 0).
+        One more camera never opens a way, so an env whose baseline has none has no eligible
+        candidate."""
+        return self.valid.bool() & (self.ticks >= 0)
+
+    def best(self) -> torch.Tensor:
+        """[N] int64: per env the eligible candidate of lowest Solver value -- the hardest camera
+        that keeps a solvable layout solvable -- the lowest index on ties, -1 where there is none."""
+        ok = self.eligible()
+        inf = torch.full_like(self.value, float("inf"))
+        v = torch.where(ok, self.value, inf)
+        low = v.min(1, keepdim=True).values
+        m = self.value.shape[1]
+        idx = torch.arange(m, device=v.device, dtype=torch.int64).reshape(1, m).expand_as(v)
+        first = torch.where(ok & (v == low), idx, torch.full_like(idx, m)).min(1).values
+        return torch.where(first < m, first, torch.full_like(first, -1))
+
+    def headroom(self) -> torch.Tensor:
+        """[N] float64: value0 - value[best], one subtraction: the optimal return the best camera
+        would still take from the Solver; 0.0 where there is no best candidate.  Negative where
+        even the hardest candidate raises the value (PlanAblation.credit's note applies)."""
+        b = self.best()
+        vb = self.value.gather(1, b.clamp(min=0).reshape(-1, 1)).reshape(-1)
+        return torch.where(b >= 0, self.value0 - vb, torch.zeros_like(self.value0))
+
+    def blocking(self) -> torch.Tensor:
+        """[N] float64: per env the share of its valid candidates that turn a solvable layout
+        unsolvable (ticks0 >= 0, the variant's ticks < 0); 0.0 for an env whose baseline is
+        unsolvable or that has no valid candidate."""
+        va = self.valid.bool()
+        blk = (va & (self.ticks < 0) & (self.ticks0 >= 0).reshape(-1, 1)).sum(1).double()
+        nv = va.sum(1).double()
+        return torch.where(nv > 0, blk / nv.clamp(min=1.0), torch.zeros_like(nv))
+
+    def metrics(self) -> dict:
+        """The trainer's three figures for this scan (AdversarialTrainer(track_camera_headroom=True)):
+        camera_headroom_envs -- the envs that have a best candidate; camera_headroom_mean -- the
+        mean headroom over them; camera_blocking_frac -- the mean of blocking() over the envs whose
+        baseline is solvable.  A mean over nothing is 0.0."""
+        has = self.best() >= 0
+        solv = self.ticks0 >= 0
+        z = torch.zeros_like(self.value0)
+        s = torch.stack([has.sum().double(), torch.where(has, self.headroom(), z).sum(), solv.sum().double(),
+                         torch.where(solv, self.blocking(), z).sum()]).cpu().tolist()
+        div = lambda a, b: a / b if b else 0.0  # noqa: E731
+        return {"camera_headroom_mean": div(s[1], s[0]), "camera_blocking_frac": div(s[3], s[2]),
+                "camera_headroom_envs": int(s[0])}
+
+
+def placement_scan(env, cands, horizon: Optional[int] = None, gamma: float = 1.0, base: Optional[torch.Tensor] = None,
+                   max_bytes: int = 1 << 30) -> PlacementScan:
+    """Every candidate camera of cands (float64 [N, M, 6] or [M, 6], camera_candidates' rows) tried
+    on every env of a HeistEnv as it stands: HeistEnv.plan_place in chunks of M sized so that a
+    chunk's visibility rows (4 H N m W bytes) stay under max_bytes, the rows dropped, the tables
+    concatenated.  base: the rows the candidates are added to (plan_place's base; None: one
+    plan_field launch supplies them).  The baseline ticks0 / value0 is the plan of those rows
+    alone, which is what plan_place gives for a candidate that is not valid (a row of NaNs): with
+    plan_field's rows it is plan_field's togo and plan_value's value at the Solver's cell.  Reads
+    the envs only."""
+    from .obs_compact import record_words
+    H = min(int(env.config.max_steps), 1024) if horizon is None else int(horizon)
+    cd = torch.as_tensor(cands)
+    if cd.dim() == 2:
+        cd = cd.unsqueeze(0).expand(env.n_envs, -1, -1)
+    cd = cd.to(env.device)
+    M = int(cd.shape[1])
+    if base is None:
+        base = env.plan_field(horizon=H).vis
+    per = 4 * max(H, 1) * env.n_envs * record_words(env.rows, env.cols)
+    step = max(1, int(max_bytes) // per)
+    nan = torch.full((1, 6), float("nan"), dtype=torch.float64, device=env.device)
+    p0 = env.plan_place(nan, horizon=H, gamma=gamma, base=base)
+    parts = []
+    for m0 in range(0, M, step):
+        pp = env.plan_place(cd[:, m0:m0 + step], horizon=H, gamma=gamma, base=base)
+        parts.append((pp.valid, pp.ticks, pp.value, pp.action))
+        del pp
+    valid, ticks, value, action = (torch.cat(x, 1) for x in zip(*parts))
+    return PlacementScan(valid, ticks, value, action, p0.ticks[:, 0], p0.value[:, 0], cd)
+
+
+@dataclass
+class RelocationScan:
+    """relocation_scan's output: scan -- the PlacementScan of the slot's camera on every interior
+    cell, over the layout without that camera (its baseline ticks0 / value0 is the layout without
+    the camera); ticks_built [N] int16, value_built [N] float64 -- the layout as built;
+    rank [N] int64 -- how many valid candidates give the Solver a strictly lower value than the
+    layout as built: 0 says the Architect's tile is optimal for this camera (-1: the env does not
+    fill the slot)."""
+    scan: PlacementScan
+    ticks_built: torch.Tensor
+    value_built: torch.Tensor
+    rank: torch.Tensor
+
+
+def relocation_scan(env, slot: int, headings=None, horizon: Optional[int] = None, gamma: float = 1.0,
+                    max_bytes: int = 1 << 30) -> RelocationScan:
+    """Where else could camera `slot` of every env have stood?  One plan_masked launch plans every
+    env as built and without the camera; its second variant's rows are the base of a
+    placement_scan whose candidates carry the camera's own fov, speed and range
+    (HeistEnv.camera_records) on every interior cell, with the heading it has now or, given
+    headings, each of those.  Reads the envs only."""
+    slot = int(slot)
+    if not 0 <= slot < env.max_cams:
+        raise ValueError("relocation_scan: slot must be a camera slot, 0 .. %d" % (env.max_cams - 1))
+    ex = env.export()
+    masks = ablation_masks(ex["n_cams"], ex["n_guards"], env.max_cams, env.max_guards)[:, [0, 1 + slot]].contiguous()
+    pm = env.plan_masked(masks, horizon=horizon, gamma=gamma)
+    rec = env.camera_records()[:, slot]                                   # [N, 6]
+    cd = camera_candidates(env.grid_snapshot(), [0.0] if headings is None else headings, 0.0, 0.0, 0.0)
+    own = rec.reshape(-1, 1, 6).expand(-1, cd.shape[1], -1)
+    cd[:, :, 2] = own[:, :, 2]
+    cd[:, :, 4:] = own[:, :, 4:]
+    if headings is None:
+        cd[:, :, 3] = own[:, :, 3]
+    scan = placement_scan(env, cd, horizon=horizon, gamma=gamma, base=pm.vis[:, :, 1].contiguous(), max_bytes=max_bytes)
+    filled = ex["n_cams"] > slot
+    lower = (scan.valid & (scan.value < pm.value[:, :1])).sum(1)
+    return RelocationScan(scan, pm.ticks[:, 0], pm.value[:, 0], torch.where(filled, lower, torch.full_like(lower, -1)))
+
+
+def greedy_cameras(env, n: int, headings, fov: float, speed: float, vision_range, horizon: Optional[int] = None,
+                   gamma: float = 1.0, max_bytes: int = 1 << 30):
+    """The exact greedy adversary, camera by camera: n rounds of placement_scan over every interior
+    cell x headings -> PlacementScan.best() -> that camera appended to the env's layout ->
+    set_layouts + reset.  The envs must be fresh from set_layout + reset (tick 0): a round's
+    prediction is the value of the rebuilt layout's first attempt.  The layouts are read back from
+    the handle (HeistEnv.layout_lists) and rebuilt with a budget of what they spent plus 3 per
+    camera added; an env stops when its camera slots are full or no candidate is eligible.
+    Returns (cameras, predicted): cameras[r] the round's choice per env as float64 [N, 6] rows
+    (NaN where the env added none), predicted[r] float64 [N] the Solver's optimal value the scan
+    predicted for the rebuilt layout (the env's current value where it added none).  Changes the
+    envs' layouts."""
+    cams_out, pred_out = [], []
+    for _ in range(int(n)):
+        layouts, spent = env.layout_lists()
+        cd = camera_candidates(env.grid_snapshot(), headings, fov, speed, vision_range)
+        scan = placement_scan(env, cd, horizon=horizon, gamma=gamma, max_bytes=max_bytes)
+        best = scan.best()
+        room = torch.as_tensor([len(l[1]) < env.max_cams for l in layouts], device=best.device)
+        best = torch.where(room, best, torch.full_like(best, -1))
+        chosen = cd.gather(1, best.clamp(min=0).reshape(-1, 1, 1).expand(-1, 1, 6)).reshape(-1, 6)
+        chosen = torch.where((best >= 0).reshape(-1, 1), chosen, torch.full_like(chosen, float("nan")))
+        vb = scan.value.gather(1, best.clamp(min=0).reshape(-1, 1)).reshape(-1)
+        pred_out.append(torch.where(best >= 0, vb, scan.value0))
+        cams_out.append(chosen)
+        budget = []
+        for e, row in enumerate(chosen.cpu().tolist()):
+            walls, cams, guards = layouts[e]
+            add = row[0] == row[0]
+            if add:
+                cams = list(cams) + [{"row": int(row[0]), "col": int(row[1]), "fov_angle": row[2], "heading": row[3],
+                                      "rotation_speed": row[4], "vision_range": int(row[5])}]
+            layouts[e] = (walls, cams, guards)
+            budget.append(int(spent[e]) + (3 if add else 0))
+        env.set_layouts(layouts, budget=budget)
+        env.reset()
+    return cams_out, pred_out

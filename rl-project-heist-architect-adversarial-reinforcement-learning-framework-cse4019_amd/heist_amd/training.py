@@ -160,7 +160,8 @@ class AdversarialTrainer:  # training.py:115-790
                  curriculum: Union[str, Sequence[Tuple], None] = None, architect_update: str = "per_layout",
                  solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
                  track_optimal: bool = False, track_optimal_return: bool = False,
-                 track_emitter_credit: bool = False):
+                 track_emitter_credit: bool = False, track_camera_headroom: bool = False, headroom_envs: int = 64,
+                 headroom_headings: int = 8):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -222,6 +223,21 @@ class AdversarialTrainer:  # training.py:115-790
         # launch, no metric, logs and checkpoints byte-identical
         self.track_emitter_credit = bool(track_emitter_credit)
         self._emitter_credit = None  # the four metrics of the latest ablated layout batch
+        # True: up to headroom_envs of every layout batch's BFS-valid envs are scanned for one more
+        # camera (search.placement_scan at gamma 1, right after the batch's set_layout + reset): a
+        # camera with the reference's default field of view, speed and range on every interior cell at
+        # headroom_headings evenly spaced headings, and train_iteration reports the latest batch's
+        # camera_headroom_mean (the optimal return the hardest such camera that keeps the layout
+        # solvable would still take from the Solver), camera_blocking_frac (the share of the placeable
+        # candidates that make a solvable layout unsolvable) and camera_headroom_envs (the envs behind
+        # the mean).  False: no launch, no metric, logs and checkpoints byte-identical
+        self.track_camera_headroom = bool(track_camera_headroom)
+        self.headroom_envs = int(headroom_envs)
+        self.headroom_headings = int(headroom_headings)
+        if self.track_camera_headroom and (self.headroom_envs < 1 or self.headroom_headings < 1):
+            raise ValueError("track_camera_headroom needs headroom_envs >= 1 and headroom_headings >= 1")
+        self._camera_headroom = None  # the three metrics of the latest scanned layout batch
+        self._headroom_env = None     # the side handle of headroom_envs envs the scan runs on
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -359,6 +375,8 @@ class AdversarialTrainer:  # training.py:115-790
                     self._value_layout_batch(good)
                 if self.track_emitter_credit:
                     self._ablate_layout_batch(good)
+                if self.track_camera_headroom:
+                    self._headroom_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
@@ -384,6 +402,40 @@ class AdversarialTrainer:  # training.py:115-790
         ab = self.env.plan_ablate(gamma=1.0)
         i = torch.as_tensor(env_ids, device=self.device)
         self._emitter_credit = PlanAblation.from_tables(ab.ticks[i], ab.value[i], ab.filled[i]).metrics(self.env.max_cams)
+
+    def _headroom_layout_batch(self, env_ids):
+        """The camera headroom of the layouts just set on env_ids (fresh after reset): the first
+        headroom_envs of them, scanned with the reference's default camera (components.security.Camera's
+        field of view, speed and range, which LayoutBatch.from_lists and the Architect's decode fall
+        back to) on every interior cell at headroom_headings headings."""
+        from .components.security import Camera
+        from .search import PlacementScan, camera_candidates, placement_scan
+        ref = Camera(0, 0)
+        ids = [int(e) for e in np.asarray(env_ids, np.int64)[:self.headroom_envs]]
+        k = self.headroom_envs
+        if self._headroom_env is None:  # a launch plans every env of its handle: the scanned ones get their own
+            self._headroom_env = HeistEnv(k, self.config, max_cams=self.env.max_cams, max_guards=self.env.max_guards,
+                                          max_path=self.env.max_path, device=self.device, auto_reset=True)
+        side = self._headroom_env
+        side.set_guard_cones(bool(self.env.kernel_config()["guard_cones"]))  # a saved state names the setting
+        # env j of the side handle <- scanned env j mod len(ids): every env holds a layout, the first len(ids) count
+        ok = side.load_state(self.env.save_state(ids), index=[j % len(ids) for j in range(k)])
+        if not bool(ok.all()):
+            raise RuntimeError("track_camera_headroom: the side handle rejected a saved env")
+        hd = [360.0 * h / self.headroom_headings for h in range(self.headroom_headings)]
+        cd = camera_candidates(side.grid_snapshot(), hd, ref.fov_angle, ref.rotation_speed, ref.vision_range)
+        sc = placement_scan(side, cd, gamma=1.0)
+        m = len(ids)
+        self._camera_headroom = PlacementScan(sc.valid[:m], sc.ticks[:m], sc.value[:m], sc.action[:m], sc.ticks0[:m],
+                                              sc.value0[:m]).metrics()
+
+    def close(self):
+        """Release the trainer's env handles: the batch's and, if a scan made one, the camera-headroom side
+        handle.  (HeistEnv also releases itself when it is collected.)"""
+        for h in (self._headroom_env, self.env):
+            if h is not None:
+                h.close()
+        self._headroom_env = None
 
     # -- rollout / scoring ------------------------------------------------------------------
     @torch.no_grad()
@@ -725,6 +777,8 @@ class AdversarialTrainer:  # training.py:115-790
             out["optimal_return_mean"] = self._optimal_return
         if self.track_emitter_credit and self._emitter_credit is not None:
             out.update(self._emitter_credit)
+        if self.track_camera_headroom and self._camera_headroom is not None:
+            out.update(self._camera_headroom)
         return out
 
     # -- supervised pre-training on exact labels (no reference counterpart) -------------------

@@ -217,6 +217,38 @@ class PlanMasked:
 
 
 @dataclass
+class PlanPlace:
+    """HeistEnv.plan_place's output (heist_plan_place, include/heist.h), device tensors; variant
+    (e, m) is env e with the candidate camera cands[e, m] added to the base rows:
+    valid [N, M] bool -- the candidate is placeable in the grid as it stands and its parameters are
+        ones the raycaster takes; an invalid candidate's variant is the base rows' plan;
+    ticks [N, M] int16 -- the fewest ticks to a clean vault arrival from the Solver's cell (-1: none);
+    value [N, M] float64, action [N, M] int8 -- the largest discounted return from there and the
+        lowest action that starts it (PlanValue's at that cell);
+    vis [H, N, M, W] int32 -- row k - 1: the variant's visibility plane of the k-th tick from now,
+        4 H N M W bytes;
+    togo_cells [N, M, R, C] int16, value_cells [N, M, R, C] float64 or None -- the whole tables
+        (PlanField.togo / PlanValue.value of the variant); with cells=True only;
+    cands [N, M, 6] float64 -- the candidates as given (row, col, fov_angle, heading,
+        rotation_speed, vision_range);
+    tick [N] int32 -- each env's tick at the call, -1 where it was done (PlanValue.tick)."""
+    valid: torch.Tensor
+    ticks: torch.Tensor
+    value: torch.Tensor
+    action: torch.Tensor
+    vis: torch.Tensor
+    togo_cells: Optional[torch.Tensor]
+    value_cells: Optional[torch.Tensor]
+    cands: torch.Tensor
+    tick: torch.Tensor
+    rows: int
+    cols: int
+    gamma: float = 1.0
+
+    vis_mask = PlanMasked.vis_mask
+
+
+@dataclass
 class PlanQ:
     """HeistEnv.plan_q's output (heist_plan_q, include/heist.h; heist_amd.search.q_values gives the
     same on any device): the exact action values of visited states, [K, N] time-major, state
@@ -635,6 +667,65 @@ class HeistEnv:
         filled = torch.where(j < mc, j < ex["n_cams"].reshape(-1, 1), j - mc < ex["n_guards"].reshape(-1, 1))
         return PlanAblation.from_tables(pm.ticks, pm.value, filled)
 
+    # -- planner placement (heist_plan_place) --------------------------------------------------
+    @property
+    def plan_place_supported(self) -> int:
+        """heist_plan_place_supported: 1 when plan_place() has a kernel for this handle (where
+        plan_masked() has one: every grid up to 32 x 32; 0 at 64 x 64)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_place_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_place_supported")
+        return d
+
+    def plan_place(self, cands, horizon: Optional[int] = None, gamma: float = 1.0, base: Optional[torch.Tensor] = None,
+                   cells: bool = False) -> "PlanPlace":
+        """heist_plan_place: every env as it stands planned with one more camera, M candidates per
+        env in one launch that casts the candidate alone -- the fewest ticks to the vault and the
+        largest discounted return from the Solver's cell over the rows of `base` ORed with the
+        candidate's cone, plus every variant's visibility planes and, with cells, the whole tables.
+        cands: float64 [N, M, 6], or [M, 6] for the same candidates on every env, each row a
+        set_layout camera (row, col, fov_angle, heading, rotation_speed, vision_range) with the
+        heading it has now.  base: the visibility rows the candidates are added to, int32
+        [H, N, W] -- PlanField.vis, PlanValue.vis or PlanMasked.vis[:, :, m] of this handle as it
+        stands -- or None, and then plan_field(horizon) supplies them.  horizon and gamma as in
+        plan_value.  vis takes 4 H N M W bytes.  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        W = record_words(R, C)
+        cd = torch.as_tensor(cands)
+        if cd.dtype != torch.float64 or cd.dim() not in (2, 3) or cd.shape[-1] != 6 or (cd.dim() == 3 and cd.shape[0] != n):
+            raise ValueError("plan_place: cands must be a float64 [%d, M, 6] or [M, 6] tensor" % n)
+        if cd.dim() == 2:
+            cd = cd.unsqueeze(0).expand(n, -1, -1)
+        cd = cd.to(self.device).contiguous()
+        M = int(cd.shape[1])
+        if base is None:
+            base = self.plan_field(horizon=H).vis if 1 <= H <= 1024 else None
+        elif (not isinstance(base, torch.Tensor) or base.dtype != torch.int32 or tuple(base.shape) != (h, n, W)
+              or base.device != self.device):
+            raise ValueError("plan_place: base must be an int32 [%d, %d, %d] tensor on %s" % (h, n, W, self.device))
+        else:
+            base = base.contiguous()
+            if base.data_ptr() % 16:  # a slice that starts off a 16-byte boundary
+                base = base.clone()
+        kw = dict(device=self.device)
+        valid = torch.empty((n, M), dtype=torch.uint8, **kw)
+        ticks = torch.empty((n, M), dtype=torch.int16, **kw)
+        value = torch.empty((n, M), dtype=torch.float64, **kw)
+        action = torch.empty((n, M), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, M, W), dtype=torch.int32, **kw)
+        tcells = torch.empty((n, M, R, C), dtype=torch.int16, **kw) if cells else None
+        vcells = torch.empty((n, M, R, C), dtype=torch.float64, **kw) if cells else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_place(self._h, H, float(gamma), M, nat.ptr(cd) if M else None, nat.ptr(base),
+                                                 nat.ptr(valid), nat.ptr(ticks), nat.ptr(value), nat.ptr(action),
+                                                 nat.ptr(vis), nat.ptr(tcells), nat.ptr(vcells), self._stream()),
+                      "heist_plan_place")
+        ex = self.export()
+        tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
+        return PlanPlace(valid.view(torch.bool), ticks, value, action, vis, tcells, vcells, cd, tick, R, C, float(gamma))
+
     # -- planner Q (heist_plan_q) --------------------------------------------------------------
     PLAN_Q_OUTPUTS = ("q", "value", "best", "optimal", "gap")
 
@@ -870,6 +961,68 @@ class HeistEnv:
             nat.check(nat.lib().heist_state_fork(self._h, nat.ptr(src), nat.ptr(dst), m, nat.ptr(status),
                                                  self._stream()), "heist_state_fork")
         return status
+
+    # -- the layouts as the handle holds them (read from the state blobs, include/heist.h) ----
+    def _layout_blobs(self) -> torch.Tensor:
+        """save_state()'s blobs [N, bytes] uint8, after a check that they are laid out as camera_records and
+        layout_lists slice them: the header's magic and format version 1 (include/heist.h) and this handle's
+        capacities."""
+        blobs = self.save_state().blobs
+        head = blobs[0, :28].cpu().contiguous().view(torch.int32).tolist()
+        want = [0x54534548, 1, self.rows, self.cols, self.max_cams, self.max_guards, self.max_path]
+        if head != want:
+            raise nat.HeistError("state blob header %r is not the format version 1 layout %r that camera_records / "
+                                 "layout_lists read" % (head, want))
+        return blobs
+
+    def camera_records(self) -> torch.Tensor:
+        """Every camera slot as a heist_set_layout cam_params row, float64 [N, max_cams, 6] = (row,
+        col, fov_angle, heading, rotation_speed, vision_range) with the heading the camera has now:
+        the 32-byte camera records of the state blobs (save_state).  Slots from n_cams[e] up hold
+        whatever the handle last kept there.  Reads the envs only."""
+        mc = self.max_cams
+        blobs = self._layout_blobs()
+        rec = blobs[:, 112:112 + 32 * mc].reshape(self.n_envs, mc, 32)
+        f = rec[:, :, :24].contiguous().view(torch.float64)              # fov, heading, speed
+        i = rec[:, :, 24:].contiguous().view(torch.int16).double()       # row, col, range, rays
+        return torch.stack([i[..., 0], i[..., 1], f[..., 0], f[..., 1], f[..., 2], i[..., 2]], -1)
+
+    def layout_lists(self):
+        """The envs' layouts as the handle holds them now, in the reference's set_layout format, and
+        what each spent: (layouts, spent) with layouts[e] = (walls, cameras, guards) -- the interior
+        wall tiles of the grid in row-major order, the filled camera slots with their current
+        headings, the filled guard slots with their patrol paths -- read from the state blobs
+        (save_state).  set_layouts(layouts, budget=spent) rebuilds the same grids and records; a
+        wall that a guard's start tile replaced is not listed, so a rebuild can spend less.  Host
+        lists; reads the envs only."""
+        mc, mg, mp = self.max_cams, self.max_guards, self.max_path
+        n, R, C = self.n_envs, self.rows, self.cols
+        blobs = self._layout_blobs().cpu()
+        sc = blobs[:, 64:112].contiguous().view(torch.int32).numpy()   # heist_export's 12 scalars
+        cams = self.camera_records().cpu().numpy()
+        g0 = 112 + 32 * mc
+        grec = blobs[:, g0:g0 + 32 * mg].reshape(n, mg, 32)
+        gf = grec[:, :, :16].contiguous().view(torch.float64).numpy()  # fov, heading
+        gi = grec[:, :, 16:26].contiguous().view(torch.int16).numpy()  # patrol index, step, length, range, rays
+        p0 = g0 + 32 * mg
+        paths = blobs[:, p0:p0 + 2 * mg * mp].contiguous().view(torch.int16).numpy().reshape(n, mg, mp)
+        q0 = p0 + ((2 * mg * mp + 15) & ~15)
+        grid = blobs[:, q0:q0 + R * C].numpy().reshape(n, R, C)
+        layouts, spent = [], []
+        for e in range(n):
+            walls = [(int(r), int(c)) for r, c in zip(*np.nonzero(grid[e, 1:R - 1, 1:C - 1] == 1))]
+            walls = [(r + 1, c + 1) for r, c in walls]
+            cl = [{"row": int(v[0]), "col": int(v[1]), "fov_angle": float(v[2]), "heading": float(v[3]),
+                   "rotation_speed": float(v[4]), "vision_range": int(v[5])} for v in cams[e, :sc[e, 8]]]
+            gl = []
+            for g in range(int(sc[e, 9])):
+                ln = int(gi[e, g, 2])
+                pts = [(int(v) & 0xff, (int(v) >> 8) & 0xff) for v in paths[e, g, :ln]]
+                gl.append({"patrol_path": pts, "speed": int(gi[e, g, 1]), "vision_range": int(gi[e, g, 3]),
+                           "fov_angle": float(gf[e, g, 0])})
+            layouts.append((walls, cl, gl))
+            spent.append(int(sc[e, 11]))
+        return layouts, spent
 
     # -- compact observation records (obs_compact.CompactObs) ---------------------------
     def grid_snapshot(self) -> torch.Tensor:

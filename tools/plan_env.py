@@ -39,6 +39,13 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # and without a critical emitter, and the launch next to the route it
                                                  # replaces, M x (heist_plan_field + heist_plan_value); also written to
                                                  # profiles/plan_masked.log
+  python tools/plan_env.py --place [--gamma G]    # the planner placement (heist_plan_place, HeistEnv.plan_place) on the
+                                                 # Architect batch: the launch at 8 candidate cameras per env next to
+                                                 # heist_plan_masked with 8 all-on masks and to the route without it
+                                                 # (set_layout_batch + reset + plan_field + plan_value on a twin handle,
+                                                 # one candidate per env per pass), then a full placement_scan of 64
+                                                 # envs x every interior cell x 8 headings with its headroom, blocking
+                                                 # and relocation-rank figures; also written to profiles/plan_place.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -413,6 +420,129 @@ def ablate_table(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def place_mode(args, dev):
+    """heist_plan_place on the Architect batch, one JSON line per row, each with its N, M and device
+    seconds per variant: (a) the launch at M = 8 candidates per env, with the same launch on
+    candidates that are not valid (no cast: the row copies and the two sweeps alone); (b)
+    heist_plan_masked on the same handle with 8 all-on masks, and with 8 all-off masks (the forward
+    loop without a ray); (c) the route without the kernel -- the candidates laid into a twin handle
+    with one more camera slot by set_layout_batch + reset + plan_field + plan_value, one candidate
+    per env per pass; (d) a full placement_scan of 64 envs x every interior cell x 8 headings, with
+    the headroom and blocking it finds and the relocation rank of every camera of those layouts."""
+    from heist_amd.components.security import Camera
+    from heist_amd.search import camera_candidates, placement_scan, relocation_scan
+    from heist_amd.vec_env import LayoutBatch
+    H = min(args.horizon or args.max_steps, 1024)
+    N, R, M = args.envs, args.grid, 8
+    ref = Camera(0, 0)
+    env = make_env(args, "architect", dev)
+    kc = env.kernel_config()
+    assert env.plan_place_supported == 1, kc
+    head = {"config": "%dx%d" % (R, R), "layouts": "architect", "horizon": H, "gamma": args.gamma,
+            "multi_waves": kc["multi_waves"], "camera": [ref.fov_angle, ref.rotation_speed, ref.vision_range]}
+    lines = []
+
+    def emit(row):
+        lines.append(json.dumps(dict(head, **row)))
+        print(lines[-1], flush=True)
+
+    def med(fn, runs=None):
+        ms = timed(dev, fn, args.warmup, runs or args.runs)
+        return statistics.median(ms), ms
+
+    # (a) M = 8 candidates per env: a random interior cell each, heading 45 m, the reference's camera
+    gen = torch.Generator().manual_seed(args.seed)
+    cell = torch.randint(1, R - 1, (N, M, 2), generator=gen).double()
+    cd = torch.cat([cell, torch.full((N, M, 1), ref.fov_angle, dtype=torch.float64),
+                    (45.0 * torch.arange(M, dtype=torch.float64)).reshape(1, M, 1).expand(N, M, 1),
+                    torch.full((N, M, 1), ref.rotation_speed, dtype=torch.float64),
+                    torch.full((N, M, 1), float(ref.vision_range), dtype=torch.float64)], 2).to(dev)
+    base = env.plan_field(H).vis
+    pp = env.plan_place(cd, H, gamma=args.gamma, base=base)
+    valid, ticks_a, value_a = pp.valid.clone(), pp.ticks.clone(), pp.value.clone()
+    del pp
+    a, a_ms = med(lambda: env.plan_place(cd, H, gamma=args.gamma, base=base))
+    nan = torch.full((N, M, 6), float("nan"), dtype=torch.float64, device=dev)
+    s, s_ms = med(lambda: env.plan_place(nan, H, gamma=args.gamma, base=base))
+    emit({"row": "a", "what": "plan_place", "envs": N, "M": M, "valid_frac": float(valid.float().mean()),
+          "launch_ms_median": a, "launch_ms": a_ms, "seconds_per_variant": a * 1e-3 / (N * M),
+          "invalid_candidates_launch_ms_median": s, "invalid_candidates_launch_ms": s_ms,
+          "sweeps_and_copy_seconds_per_variant": s * 1e-3 / (N * M),
+          "forward_seconds_per_variant": (a - s) * 1e-3 / (N * M)})
+
+    # (b) plan_masked, 8 all-on masks (every emitter cast per variant) and 8 all-off masks
+    on = torch.full((N, M), -1, dtype=torch.int64, device=dev)
+    b, b_ms = med(lambda: env.plan_masked(on, H, gamma=args.gamma))
+    o, o_ms = med(lambda: env.plan_masked(torch.zeros_like(on), H, gamma=args.gamma))
+    x = env.export()
+    emit({"row": "b", "what": "plan_masked all-on", "envs": N, "M": M,
+          "emitters_per_env_mean": float((x["n_cams"] + x["n_guards"]).float().mean()),
+          "launch_ms_median": b, "launch_ms": b_ms, "seconds_per_variant": b * 1e-3 / (N * M),
+          "all_off_launch_ms_median": o, "all_off_launch_ms": o_ms, "all_off_seconds_per_variant": o * 1e-3 / (N * M),
+          "place_over_masked": a / b})
+
+    # (c) the route without the kernel: candidate 0 of every env as a camera of a twin's layout
+    layouts, spent = env.layout_lists()
+    c0 = cd[:, 0].cpu().tolist()
+    plus = [(w, cams + [{"row": int(v[0]), "col": int(v[1]), "fov_angle": v[2], "heading": v[3], "rotation_speed": v[4],
+                         "vision_range": int(v[5])}], g) for (w, cams, g), v in zip(layouts, c0)]
+    twin = HeistEnv(N, env.config, max_cams=env.max_cams + 1, max_guards=env.max_guards, max_path=env.max_path,
+                    device=dev, auto_reset=True)
+    lb = LayoutBatch.from_lists(plus, [sp + 3 for sp in spent], twin.max_cams, twin.max_guards, twin.max_path, dev, R, R)
+    sr, sc = env.config.start_pos
+
+    def route():
+        twin.set_layout_batch(lb)
+        twin.reset()
+        return twin.plan_field(H), twin.plan_value(H, gamma=args.gamma)
+
+    pf, pv = route()
+    v0 = valid[:, 0]
+    same = bool(torch.equal(pf.togo[:, sr, sc][v0], ticks_a[:, 0][v0])
+                and torch.equal(pv.value[:, sr, sc][v0].contiguous().view(torch.int64),
+                                value_a[:, 0][v0].contiguous().view(torch.int64)))
+    del pf, pv
+    c, c_ms = med(route)
+    emit({"row": "c", "what": "set_layout_batch + reset + plan_field + plan_value on a twin handle", "envs": N, "M": 1,
+          "twin_equals_plan_place_bitwise_on_valid_candidates": same,
+          "pass_ms_median": c, "pass_ms": c_ms, "seconds_per_variant": c * 1e-3 / N, "route_over_place": (c / N) / (a / (N * M))})
+    twin.close()
+
+    # (d) a full scan: 64 envs, every interior cell, 8 headings; then every camera's relocation rank
+    n = min(64, N)
+    side = HeistEnv(n, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                    auto_reset=True)
+    assert bool(side.load_state(env.save_state(list(range(n)))).all())
+    full = camera_candidates(side.grid_snapshot(), [45.0 * h for h in range(8)], ref.fov_angle, ref.rotation_speed,
+                             ref.vision_range)
+    scan = placement_scan(side, full, H, gamma=args.gamma)
+    d, d_ms = med(lambda: placement_scan(side, full, H, gamma=args.gamma), runs=min(args.runs, 3))
+    Mf = int(full.shape[1])
+    solv = scan.ticks0 >= 0
+    ranks, n_valid = [], []
+    for j in range(side.max_cams):
+        rs = relocation_scan(side, j, horizon=H, gamma=args.gamma)
+        keep = rs.rank >= 0
+        ranks += rs.rank[keep].cpu().tolist()
+        n_valid += rs.scan.valid.sum(1)[keep].cpu().tolist()
+    emit({"row": "d", "what": "placement_scan, every interior cell x 8 headings", "envs": n, "M": Mf,
+          "scan_ms_median": d, "scan_ms": d_ms, "seconds_per_variant": d * 1e-3 / (n * Mf),
+          "valid_frac": float(scan.valid.float().mean()), "solvable_baselines": int(solv.sum()), **scan.metrics(),
+          "headroom_max": float(scan.headroom().max()), "value0_mean": float(scan.value0.mean()),
+          "blocking_frac_max": float(scan.blocking().max()),
+          "relocation": {"cameras": len(ranks), "rank0_frac": sum(r == 0 for r in ranks) / max(1, len(ranks)),
+                         "rank_median": statistics.median(ranks) if ranks else None,
+                         "rank_mean": sum(ranks) / max(1, len(ranks)),
+                         "valid_tiles_mean": sum(n_valid) / max(1, len(n_valid))}})
+    side.close()
+    env.close()
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_place.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --place --gamma %r\n" % args.gamma)
+        fh.write("\n".join(lines) + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -433,7 +563,7 @@ def main(argv=None):
                     "togo_ticks / value_ticks and action_ticks")
     ap.add_argument("--value", action="store_true", help="time heist_plan_value next to heist_plan_field on all three "
                     "batches, with the start cell's values and the length of the return-optimal episodes")
-    ap.add_argument("--gamma", type=float, default=1.0, help="with --value / --ablate: the discount")
+    ap.add_argument("--gamma", type=float, default=1.0, help="with --value / --ablate / --place: the discount")
     ap.add_argument("--play", action="store_true", help="time heist_plan_play next to the Python path it replaces and "
                     "to heist_plan_value on the --layouts batch")
     ap.add_argument("--noise", type=float, default=0.1, help="with --play / --q: the noisy play's probability")
@@ -441,11 +571,16 @@ def main(argv=None):
                     "tensors and to the plan_value(all_ticks=True) launch that feeds it, on all three batches")
     ap.add_argument("--ablate", action="store_true", help="time heist_plan_masked's leave-one-out launch next to "
                     "M x (heist_plan_field + heist_plan_value) on all three batches, with the critical / redundant emitters")
+    ap.add_argument("--place", action="store_true", help="time heist_plan_place next to heist_plan_masked and to the "
+                    "twin-handle route on the Architect batch, then a full placement_scan of 64 envs")
     ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
-                    "profiles/plan_play.log, --q's: profiles/plan_q.log, --ablate's: profiles/plan_masked.log)")
+                    "profiles/plan_play.log, --q's: profiles/plan_q.log, --ablate's: profiles/plan_masked.log, --place's: "
+                    "profiles/plan_place.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.place:
+        return place_mode(args, dev)
     if args.ablate:
         return ablate_table(args, dev)
     if args.q:
