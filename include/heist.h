@@ -480,6 +480,76 @@ int heist_plan_place(heist_t h, int horizon, double gamma, int M, const double* 
                      int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
                      double* value_cells_out, heist_stream_t stream);
 
+/* Planner placement for guards, no reference counterpart: heist_plan_place's question with a guard
+ * as the candidate -- M candidate guards per env in one launch, which tells where the Architect's
+ * most expensive asset (5 points), and its only moving one, would have mattered.  The premise is the
+ * camera's: an emitter blocks neither a ray nor a move, and a guard whose patrol starts on an EMPTY
+ * tile leaves the wall plane alone (heist_set_layout marks only the start tile, as kGuard), so the
+ * visibility of "this layout plus guard X" on a tick is the layout's own row OR X's cone OR X's own
+ * cell on that tick.  The launch casts the candidate alone, against the env's wall plane; none of
+ * the env's own emitters is read or cast.
+ *   cand_path [N][M][P][2] int32, 4-byte aligned, 1 <= P <= 64: the patrol points (row, col) of
+ *            candidate (e, m); only its first len points are read.
+ *   cand_meta [N][M][4] int32, 4-byte aligned: len, speed, vision_range, idx.  idx is the patrol
+ *            index the guard stands on now, at env e's current tick (0 for a guard as
+ *            heist_set_layout leaves it).
+ *   cand_fov  [N][M][2] float64, 8-byte aligned: fov_angle, heading.  heading is the guard's heading
+ *            now (0.0 as heist_set_layout leaves it).
+ *            The record is heist_set_layout's own conversion of an accepted guard: step = speed mod
+ *            len (Python's %, never negative), range (int16)vision_range, max(int(fov_angle * 2),
+ *            30) rays, pos0 = path[0], pos = path[idx], raycast live (no cone cache entry).  A
+ *            heading with |heading| > 360, which no env guard ever holds (theirs is 0.0 or an entry
+ *            of the handle's heading table), is first brought into [0, 360) by Python's % 360: the
+ *            same direction.
+ *   base_vis, gamma, horizon, M: heist_plan_place's, with the same meaning, layout and alignment.
+ * Candidate (e, m) is valid iff all of these hold, every comparison false for a NaN:
+ *   1. 1 <= len <= P and 0 <= idx < len;
+ *   2. every one of the len points lies inside the grid, 0 <= r < R and 0 <= c < C
+ *      (heist_set_layout's precondition; nothing is clamped here);
+ *   3. path[0] is placeable as it stands (environment.py:160-167): 0 < r < R-1, 0 < c < C-1 and the
+ *      tile is EMPTY.  Later points may be any tile, wall and border included: the env's guards
+ *      walk such paths and the candidate does what they do;
+ *   4. 0 < fov_angle <= 16000;
+ *   5. |heading| <= 1e300;
+ *   6. 0 <= vision_range < 32768.
+ *   The budget, the guard slots and the handle's max_path are ignored: a handle created with
+ *   max_guards = 0, or with no emitter slot at all, is served.  No int32 or float64 bit pattern in
+ *   the three arrays makes the launch read or write out of bounds: the points are read only once
+ *   1. and 4. - 6. hold, and an invalid candidate is never converted and never cast.
+ *   valid_out [N][M] uint8: 1 for a valid candidate, else 0 (whatever HK is).
+ * Variant (e, m) is planned as heist_plan_place plans one, HK = min(horizon, max_steps - tick[e])
+ * ticks (0 for an env already done), over
+ *   vis_k(e, m) = base_vis[k-1][e] | cone_k(e, m) | own cell_k(e, m),   k = 1 .. HK.
+ * On tick k the guard first patrols (security.py:145-159): with len >= 2, idx = (idx + step) mod len
+ * and pos = path[idx]; its heading becomes the handle's heading-table entry of the move when the
+ * position changed, and is kept otherwise.  It then marks its own cell (visibility.py:59) and casts
+ * from pos with the handle's ray_mode on the path a live-raycast env guard takes (whole-tile
+ * samples; fp32 fast path, tie buckets, exact recast of near-tie rays; exact-only above range 6).
+ * A range of 0 casts nothing and marks the own cell only.  An invalid candidate's variant is the
+ * base rows' plan.
+ *   ticks_out, value_out, action_out, vis_out, togo_cells_out, value_cells_out: heist_plan_place's
+ *            outputs of the same names, shapes, alignments, padding and HK = 0 fill (-1 / 0.0 / -1,
+ *            rows k > HK and pad words 0).
+ * With heist_plan_field's rows as base_vis, a valid candidate's variant is heist_plan_field /
+ * heist_plan_value, bit for bit, on a handle built from the same layout with the candidate appended
+ * to its guard list (budget + 5, one more guard slot, max_path >= len) and brought to the same
+ * state, whether that handle serves the guard from its cone cache or casts it live.  With the rows
+ * of a heist_plan_masked variant that switches a guard off it is that guard's relocation.
+ * The launch only reads the env.
+ * heist_plan_place_guard_supported: heist_plan_place_supported's value.  -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, gamma not finite or outside [0, 1], M < 1 or N M >= 2^31,
+ * P outside 1..64, a NULL cand_path, cand_meta, cand_fov, base_vis, valid_out, ticks_out, value_out,
+ * action_out or vis_out, base_vis or vis_out not 16-byte aligned, cand_fov, value_out or
+ * value_cells_out not 8-byte aligned, cand_path or cand_meta not 4-byte aligned, ticks_out or
+ * togo_cells_out not 2-byte aligned, a probe mode armed (HEIST_PROBE_MODE),
+ * heist_plan_place_guard_supported 0. */
+int heist_plan_place_guard_supported(heist_t h);
+int heist_plan_place_guard(heist_t h, int horizon, double gamma, int M, int P, const int32_t* cand_path,
+                           const int32_t* cand_meta, const double* cand_fov, const uint32_t* base_vis,
+                           uint8_t* valid_out, int16_t* ticks_out, double* value_out, int8_t* action_out,
+                           uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
+                           heist_stream_t stream);
+
 /* Planner playout, no reference counterpart: one episode per env played from a planner's per-tick
  * tables -- the table's own (expert) play, or that play perturbed on a counter-hashed share of the
  * steps, every visited state still labelled by the table.  The emitters do not depend on the

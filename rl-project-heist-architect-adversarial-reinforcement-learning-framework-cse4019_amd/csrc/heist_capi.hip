@@ -44,6 +44,11 @@ hipError_t launch_plan_place(const EnvParams& p, int horizon, double gamma, int 
                              const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
                              int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
                              hipStream_t st);
+hipError_t launch_plan_place_guard(const EnvParams& p, int horizon, double gamma, int M, int P,
+                                   const int32_t* cand_path, const int32_t* cand_meta, const double* cand_fov,
+                                   const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
+                                   int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                                   double* value_cells_out, hipStream_t st);
 hipError_t launch_plan_play(const EnvParams& p, int horizon, const int8_t* action_table, const uint32_t* vis,
                             const double* value_table, const int32_t* pos0, uint32_t noise_q24, uint64_t seed,
                             int64_t* actions_out, int8_t* expert_out, double* value_out, uint32_t* records_out,
@@ -700,6 +705,46 @@ int heist_plan_place(heist_t h, int horizon, double gamma, int M, const double* 
   return check_hip(heist::launch_plan_place(q, horizon, gamma, M, cand, base_vis, valid_out, ticks_out, value_out,
                                             action_out, vis_out, togo_cells_out, value_cells_out, (hipStream_t)stream),
                    "heist_plan_place");
+}
+
+int heist_plan_place_guard_supported(heist_t h) { return heist_plan_place_supported(h); }
+
+int heist_plan_place_guard(heist_t h, int horizon, double gamma, int M, int P, const int32_t* cand_path,
+                           const int32_t* cand_meta, const double* cand_fov, const uint32_t* base_vis,
+                           uint8_t* valid_out, int16_t* ticks_out, double* value_out, int8_t* action_out,
+                           uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
+                           heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_place_guard: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "heist_plan_place_guard: need 0 <= gamma <= 1");
+  HEIST_REQUIRE(M >= 1 && (int64_t)h->p.n_envs * (int64_t)M <= 0x7fffffffll,
+                "heist_plan_place_guard: need M >= 1 and N * M < 2^31");
+  HEIST_REQUIRE(P >= 1 && P <= 64, "heist_plan_place_guard: need 1 <= P <= 64");
+  HEIST_REQUIRE(cand_path && cand_meta && cand_fov && base_vis && valid_out && ticks_out && value_out && action_out &&
+                    vis_out,
+                "heist_plan_place_guard: null cand_path, cand_meta, cand_fov, base_vis or output");
+  HEIST_REQUIRE(((uintptr_t)vis_out & 15) == 0 && ((uintptr_t)base_vis & 15) == 0,
+                "heist_plan_place_guard: base_vis and vis_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)cand_fov & 7) == 0 && ((uintptr_t)value_out & 7) == 0 &&
+                    ((uintptr_t)value_cells_out & 7) == 0,
+                "heist_plan_place_guard: cand_fov / value_out / value_cells_out must be 8-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)cand_path & 3) == 0 && ((uintptr_t)cand_meta & 3) == 0,
+                "heist_plan_place_guard: cand_path / cand_meta must be 4-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)ticks_out & 1) == 0 && ((uintptr_t)togo_cells_out & 1) == 0,
+                "heist_plan_place_guard: ticks_out / togo_cells_out misaligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan_place_guard: a probe mode is armed (HEIST_PROBE_MODE)");
+  HEIST_REQUIRE(heist::plan_value_variant_exists(h->p),
+                "heist_plan_place_guard: no placement kernel for this handle "
+                "(heist_plan_place_guard_supported is 0)");
+  // the launch's own EnvParams, as heist_plan_place's: no shared fan (the candidate is cast live)
+  EnvParams q = h->p;
+  q.fan_on = 0;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  return check_hip(heist::launch_plan_place_guard(q, horizon, gamma, M, P, cand_path, cand_meta, cand_fov, base_vis,
+                                                  valid_out, ticks_out, value_out, action_out, vis_out, togo_cells_out,
+                                                  value_cells_out, (hipStream_t)stream),
+                   "heist_plan_place_guard");
 }
 
 int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const uint32_t* vis, const double* value_table,

@@ -3568,6 +3568,327 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ
 }
 
 // ---------------------------------------------------------------------------
+// Planner placement for guards (heist_plan_place_guard): ticks and return with one more guard
+// ---------------------------------------------------------------------------
+//
+// plan_place_kernel's question with a guard as the candidate (include/heist.h).  The premise is
+// the camera's: a guard blocks neither a ray nor a move, and one whose patrol starts on an EMPTY
+// tile leaves the wall plane alone, so the variant's vis_k is the caller's base row k OR the
+// candidate's cone on tick k OR its own cell.  The candidate is slot 0 of a one-slot emitter table,
+// a live-raycast guard (kind 1): each tick it patrols as plan_masked_kernel's live guard does
+// (index, point, heading from the handle's heading table), marks its own cell and casts.  Its
+// record lives in wave 0's registers; its patrol points live there too, point j in lane j (P <=
+// 64), fetched by lane index -- not in L.path, which a handle without guard slots does not have.
+// A range of 0 publishes no ray chunk (kind -1) and marks the own cell only.  An invalid candidate
+// is never converted and copies the base rows.
+// Backward passes: plan_masked_kernel's two sweeps (a copy: each planner's instances keep their
+// registers), the LDS is plan_value_lds.
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_place_guard_kernel(
+    EnvParams p, int H, double gamma, int M, int P, const int32_t* __restrict__ cand_path,
+    const int32_t* __restrict__ cand_meta, const double* __restrict__ cand_fov,
+    const uint32_t* __restrict__ base_vis, uint8_t* __restrict__ valid_out, int16_t* __restrict__ ticks_out,
+    double* __restrict__ value_out, int8_t* __restrict__ action_out, uint32_t* vis_out,
+    int16_t* __restrict__ togo_cells_out, double* __restrict__ value_cells_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr uint32_t kNone = 0xFFFFu;
+  const int oi = uni((int)(blockIdx.x / (uint32_t)M)), var = uni((int)blockIdx.x - oi * M);
+  const int e = p.dispatch_order ? (p.order[oi] & kOrderEnvMask) : oi;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, C = p.C;
+  const size_t NM = (size_t)p.n_envs * (size_t)M, em = (size_t)e * (size_t)M + (size_t)var;  // rows per tick, this row
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  // plan_masked_kernel's carve-up (plan_value_lds); the record array and L.path are not used
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // the guard plane: cleared, never stamped
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6;
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;  // the record's words (obs_record_words)
+  double* val = reinterpret_cast<double*>(uq + 128 * W);           // [2][RC] values, tick parity (16-byte aligned)
+  uint16_t* togo = reinterpret_cast<uint16_t*>(val);               // [2][RC] ticks to go, over val's first array
+  uint32_t* vrow = reinterpret_cast<uint32_t*>(val + 2 * RC);      // [2][nvis] visibility rows, tick parity
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;  // not used: the env's own emitters are not cast, and their loads fall away
+    prefetch<NT>(p, e, eb, L, raw);
+  }
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  // the candidate's words, the same in every lane; every test fails for a NaN, and nothing past them is read or
+  // converted unless they hold (include/heist.h, validity 1, 4, 5, 6)
+  const int32_t* gm = cand_meta + em * 4;
+  const int len = uni(gm[0]), speed = uni(gm[1]), vrange = uni(gm[2]), idx0 = uni(gm[3]);
+  const double fov = cand_fov[em * 2], hd0 = cand_fov[em * 2 + 1];
+  const bool words_ok = uni((int)(len >= 1 && len <= P && idx0 >= 0 && idx0 < len && vrange >= 0 && vrange < 32768 &&
+                                  fov > 0.0 && fov <= 16000.0 && __builtin_fabs(hd0) <= 1e300)) != 0;
+  // patrol point j in lane j of every wave (len <= P <= 64), packed as the env's paths are; a point outside the
+  // grid is not packed (validity 2)
+  uint32_t pt = 0u;
+  bool in_grid = true;
+  if (words_ok && lane < len) {
+    const int32_t* src = cand_path + (em * (size_t)P + (size_t)lane) * 2;
+    const int pr = src[0], pc = src[1];
+    in_grid = pr >= 0 && pr < p.R && pc >= 0 && pc < C;
+    if (in_grid) pt = (uint32_t)pack_rc(pr, pc);
+  }
+  const bool path_ok = words_ok && __ballot(!in_grid) == 0ull;
+  const uint32_t pt0 = (uint32_t)uni((int)pt);  // lane 0: patrol point 0 (0 if the path is not ok)
+  const int r0 = unpack_r((uint16_t)pt0), c0 = unpack_c((uint16_t)pt0);
+  const bool inside = path_ok && r0 > 0 && r0 < p.R - 1 && c0 > 0 && c0 < C - 1;  // validity 3, environment.py:160-167
+  __syncthreads();  // grid and stop map in LDS
+  const bool valid = uni((int)(inside && L.grid[inside ? r0 * C + c0 : 0] == kEmpty)) != 0;
+  if (t == 0) valid_out[em] = valid ? 1 : 0;
+  // the candidate's record, set_layout_kernel's conversion of an accepted guard, in every lane's registers
+  // (wave-uniform); wave 0 patrols its copy and lane 0 casts it
+  Guard gd{};
+  if (valid) {
+    gd.fov = fov;
+    // a heading the env never holds (a guard's is 0.0 or a heading-table entry, within [-360, 360]) is brought
+    // into [0, 360), the same direction: the raycaster's angle reductions are for bounded angles only
+    gd.heading = __builtin_fabs(hd0) <= 360.0 ? hd0 : py_mod360(hd0);
+    int st = speed % len;  // Python % (non-negative for len > 0)
+    if (st < 0) st += len;
+    gd.step = (int16_t)st;
+    gd.len = (int16_t)len;
+    gd.idx = (int16_t)idx0;
+    gd.range = (int16_t)vrange;
+    gd.num_rays = (int16_t)num_rays_for(fov);
+    gd.pos = (uint16_t)__shfl((int)pt, idx0, 64);
+    gd.pos0 = (uint16_t)pt0;
+    gd.hslot = kUncached;
+    gd.nslot = kUncached;
+  }
+
+  // cell / C as a multiply-shift (plan_kernel)
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+  // word t of base row k (row k is the base's vis_{k+1}); nvis <= NT: launch_plan_place_guard requires
+  // plan_value_variant_exists, which holds only where ceil(R C / 32) <= 64 W
+  auto base_word = [&](int k) -> uint32_t {
+    return t < nvis ? base_vis[((size_t)k * (size_t)p.n_envs + (size_t)e) * WR + t] : 0u;
+  };
+
+  // ---- forward: vis_1 .. vis_HK into the variant's rows of vis_out
+  if (valid) {
+    uint32_t bw = HK > 0 ? base_word(0) : 0u;
+    for (int k = 1; k <= HK; ++k) {
+      // (the barrier that closed the previous tick's pack also closed its readers of vis / em)
+      if (w0) {
+        // the guard patrols (security.py:145-159), as plan_masked_kernel's live guard does
+        const bool moves = gd.len >= 2;
+        int nidx = gd.idx;
+        if (moves) {
+          nidx += gd.step;
+          if (nidx >= gd.len) nidx -= gd.len;
+        }
+        const uint16_t np = moves ? (uint16_t)__shfl((int)pt, nidx, 64) : gd.pos;
+        if (moves)
+          gd.heading = guard_heading_after(p, unpack_r(np) - unpack_r(gd.pos), unpack_c(np) - unpack_c(gd.pos),
+                                           gd.heading);
+        gd.idx = (int16_t)nidx;
+        gd.pos = np;
+        Emit E;
+        E.kind = -1;
+        if (t == 0) {
+          E = guard_emit(gd);
+          // a range of 0 has no sample: no ray chunk (march_fast's clamped form would repeat sample n_samp = 0)
+          if (gd.range == 0) E.kind = -1;
+        }
+        publish_emitters(L, E, 1);
+      }
+      // the planner kernels' clear: it also zeroes the guard plane, which nothing stamps or reads here
+      clear_planes<NT>(p, L, gvis, true);
+      __syncthreads();  // emitter table, cleared plane
+      if (t == 0) L.vis[L.at(unpack_r(gd.pos), unpack_c(gd.pos))] = 1;  // visibility.py:59
+      cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+      const uint32_t bnext = k < HK ? base_word(k) : 0u;  // lands during the next tick's cast
+      __syncthreads();  // plane complete
+
+      // the candidate's cone and cell, 64 cells per ballot, as the two words of its chunk
+      uint32_t* cone = vrow + (k & 1) * nvis;
+      for (int ch = wave; ch < n_chunk; ch += W) {
+        const int cell = 64 * ch + lane;
+        bool seen = false;
+        if (cell < RC) {
+          const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+          seen = L.vis[L.at(r, c)] != 0;
+        }
+        const unsigned long long m = __ballot(seen);
+        if (lane < 2 && 2 * ch + lane < nvis) cone[2 * ch + lane] = (uint32_t)(m >> (32 * lane));
+      }
+      __syncthreads();  // the plane's readers are done; the cone's words complete
+      // (the next writer of this parity's words is two ticks on, behind two more barriers)
+      uint32_t* row = vis_out + ((size_t)(k - 1) * NM + em) * WR;
+      for (int i = t; i < WR; i += NT) row[i] = i < nvis ? (cone[i] | bw) : 0u;  // i < nvis: i == t; pad words 0
+      bw = bnext;
+    }
+  } else {
+    for (int k = 1; k <= HK; ++k) {
+      const uint32_t bw = base_word(k - 1);
+      uint32_t* row = vis_out + ((size_t)(k - 1) * NM + em) * WR;
+      for (int i = t; i < WR; i += NT) row[i] = i < nvis ? bw : 0u;
+    }
+  }
+
+  // the rows this variant did not run, 16 bytes per store (WR is a multiple of 4, vis_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - HK) * q4; i += NT) {
+      const int r = HK + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(vis_out + ((size_t)r * NM + em) * WR)[q] = z;
+    }
+  }
+  if (HK == 0) {  // block-uniform: an env already done (or past max_steps) has no plan and collects nothing
+    if (t == 0) {
+      ticks_out[em] = (int16_t)-1;
+      value_out[em] = 0.0;
+      action_out[em] = (int8_t)-1;
+    }
+    for (int x = t; x < RC; x += NT) {
+      if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)-1;
+      if (value_cells_out) value_cells_out[em * RC + x] = 0.0;
+    }
+    return;
+  }
+
+  // row k of vis_out is vis_{k+1}
+  auto load_row = [&](int k) {
+    return __hip_atomic_load(vis_out + ((size_t)k * NM + em) * WR + (t < nvis ? t : 0), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const int vr = p.vr, vc = p.vc, vcell = vr * C + vc;
+  const int pcell = uni(s.pos_r) * C + uni(s.pos_c);  // the Solver's cell
+
+  // ---- backward, ticks: togo_{HK-1} .. togo_0 (plan_masked_kernel's sweep)
+  __threadfence();  // this variant's rows visible to the lanes that read them back
+  __syncthreads();  // the forward pass's last readers of the visibility-row words are done
+  for (int x = t; x < RC; x += NT) togo[(HK & 1) * RC + x] = (uint16_t)kNone;  // togo_HK
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;          // vis_{k+1}
+    const uint16_t* nxt = togo + ((k + 1) & 1) * RC;     // togo_{k+1}
+    uint16_t* cur = togo + (k & 1) * RC;                 // togo_k
+    for (int x = t; x < RC; x += NT) {
+      uint32_t best = kNone;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        auto tg = [&](int y) -> uint32_t {
+          if ((vk[y >> 5] >> (y & 31)) & 1u) return kNone;
+          if (y == vcell) return 1u;
+          const uint32_t v = nxt[y];
+          return v == kNone ? kNone : v + 1u;
+        };
+        auto moved = [&](bool in_grid_, int y) { return in_grid_ && L.grid[y] != kWall ? y : x; };
+        best = tg(x);
+        uint32_t v = tg(moved(r > 0, x - C));
+        if (v < best) best = v;
+        v = tg(moved(r + 1 < p.R, x + C));
+        if (v < best) best = v;
+        v = tg(moved(c > 0, x - 1));
+        if (v < best) best = v;
+        v = tg(moved(c + 1 < C, x + 1));
+        if (v < best) best = v;
+      }
+      cur[x] = (uint16_t)best;
+      if (k == 0) {
+        if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)(uint16_t)best;
+        if (x == pcell) ticks_out[em] = (int16_t)(uint16_t)best;
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // togo_k and vis_k complete; their previous holders' readers are done
+  }
+
+  // ---- backward, return: V_{HK-1} .. V_0 (plan_masked_kernel's sweep) over the same rows; the
+  // barrier above closed the last readers of togo and of both visibility rows
+  for (int x = t; x < RC; x += NT) val[(HK & 1) * RC + x] = 0.0;  // V_HK
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  const int D0 = uni(s.initial_dist);
+  const bool bonus = D0 > 3;
+  const double r_step = p.r_step, r_detect = p.r_detect, r_vault = p.r_vault;
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;        // vis_{k+1}
+    const double* nxt = val + ((k + 1) & 1) * RC;      // V_{k+1}
+    double* cur = val + (k & 1) * RC;                  // V_k
+    const bool last = tick0 + k + 1 >= p.max_steps;    // the env times out on this tick (k = HK - 1 only)
+    for (int x = t; x < RC; x += NT) {
+      double best = 0.0;
+      int act = -1;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        const int dx = iabs_(r - vr) + iabs_(c - vc);
+        // q of the move to cell y = (yr, yc): step_multi_body's reward in its order, then the tail
+        auto q = [&](int y, int yr, int yc) -> double {
+          const int curr = iabs_(yr - vr) + iabs_(yc - vc);
+          double rew = r_step;
+          rew += (double)(dx - curr) * 0.1;
+          if (curr <= 3 && bonus) rew += 0.05 * (double)(3 - curr);
+          const bool seen = ((vk[y >> 5] >> (y & 31)) & 1u) != 0u;
+          if (seen) rew += r_detect;
+          if (y == vcell) rew += r_vault;
+          if (last) {
+            double frac = 1.0 - (double)curr / (double)(D0 > 1 ? D0 : 1);
+            if (frac < 0.0) frac = 0.0;
+            rew += frac * 2.0;
+          }
+          const double on_ = rew + gamma * nxt[y];
+          return (seen || y == vcell || last) ? rew : on_;
+        };
+        best = q(x, r, c);
+        act = 0;
+        bool ok = r > 0 && L.grid[x - C] != kWall;
+        double v = ok ? q(x - C, r - 1, c) : best;
+        if (v > best) best = v, act = 1;
+        ok = r + 1 < p.R && L.grid[x + C] != kWall;
+        v = ok ? q(x + C, r + 1, c) : best;
+        if (v > best) best = v, act = 2;
+        ok = c > 0 && L.grid[x - 1] != kWall;
+        v = ok ? q(x - 1, r, c - 1) : best;
+        if (v > best) best = v, act = 3;
+        ok = c + 1 < C && L.grid[x + 1] != kWall;
+        v = ok ? q(x + 1, r, c + 1) : best;
+        if (v > best) best = v, act = 4;
+      }
+      cur[x] = best;
+      if (k == 0) {
+        if (value_cells_out) value_cells_out[em * RC + x] = best;
+        if (x == pcell) {
+          value_out[em] = best;
+          action_out[em] = (int8_t)act;
+        }
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // V_k and vis_k complete; their previous holders' readers are done
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Lean K-tick kernel (heist_step_multi, one wave per env, grids up to 20 x 20)
 // ---------------------------------------------------------------------------
 //
@@ -5281,6 +5602,28 @@ hipError_t launch_plan_place(const EnvParams& p, int horizon, double gamma, int 
   }
   HEIST_MULTI_VARIANTS(HEIST_PLACE_CASE)
 #undef HEIST_PLACE_CASE
+  return hipErrorInvalidValue;  // not reached
+}
+
+// heist_plan_place_guard: heist_plan_place's instances, LDS, support and grid of workgroups.
+hipError_t launch_plan_place_guard(const EnvParams& p, int horizon, double gamma, int M, int P,
+                                   const int32_t* cand_path, const int32_t* cand_meta, const double* cand_fov,
+                                   const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
+                                   int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                                   double* value_cells_out, hipStream_t st) {
+  if (!plan_value_variant_exists(p) || M < 1 || (size_t)p.n_envs * (size_t)M > 0x7fffffffull || P < 1 || P > 64)
+    return hipErrorInvalidValue;
+  const size_t lds = plan_value_lds(p);
+  const unsigned blocks = (unsigned)p.n_envs * (unsigned)M;
+#define HEIST_PLACE_GUARD_CASE(W, D)                                                                              \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                     \
+    hipLaunchKernelGGL((plan_place_guard_kernel<W, D>), dim3(blocks), dim3(64 * W), lds, st, p, horizon, gamma,   \
+                       M, P, cand_path, cand_meta, cand_fov, base_vis, valid_out, ticks_out, value_out,           \
+                       action_out, vis_out, togo_cells_out, value_cells_out);                                     \
+    return hipGetLastError();                                                                                     \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_PLACE_GUARD_CASE)
+#undef HEIST_PLACE_GUARD_CASE
   return hipErrorInvalidValue;  // not reached
 }
 

@@ -11,6 +11,7 @@ from .vec_env import (HeistEnv, LayoutBatch, PlanField, PlanMasked, PlanPlace, P
                       PlanValue, STATUS_NAMES)
 from .obs_compact import CompactObs, record_cells  # noqa: F401
 from .env_state import EnvState  # noqa: F401
-from .search import (ExpertData, LookaheadResult, PlacementScan, PlanAblation, RelocationScan, ablation_masks,  # noqa: F401
-                     camera_candidates, exhaustive_lookahead, expert_data, expert_labels, expert_rollout,
-                     follow_field, greedy_cameras, placement_scan, play_table, q_values, relocation_scan)
+from .search import (ExpertData, GreedyAdversary, LookaheadResult, PlacementScan, PlanAblation, RelocationScan,  # noqa: F401
+                     ablation_masks, architect_patrol, camera_candidates, exhaustive_lookahead, expert_data,
+                     expert_labels, expert_rollout, follow_field, greedy_adversary, greedy_cameras, greedy_pick,
+                     guard_candidates, guard_placement_scan, placement_scan, play_table, q_values, relocation_scan)

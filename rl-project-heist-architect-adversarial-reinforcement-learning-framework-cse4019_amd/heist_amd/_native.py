@@ -43,6 +43,8 @@ SIGNATURES = {
     "heist_plan_masked": (_i, [_vp, _i, _d, _i] + [_vp] * 8),
     "heist_plan_place_supported": (_i, [_vp]),
     "heist_plan_place": (_i, [_vp, _i, _d, _i] + [_vp] * 10),
+    "heist_plan_place_guard_supported": (_i, [_vp]),
+    "heist_plan_place_guard": (_i, [_vp, _i, _d, _i, _i] + [_vp] * 12),
     "heist_plan_play": (_i, [_vp, _i, _vp, _vp, _vp, _vp, ctypes.c_uint32, ctypes.c_uint64] + [_vp] * 9),
     "heist_plan_q": (_i, [_vp, _i, _i, _d] + [_vp] * 11),
     "heist_export": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -25,6 +25,11 @@ camera_candidates, placement_scan, relocation_scan and greedy_cameras ask the Ar
 the question with heist_plan_place (HeistEnv.plan_place): what one more camera on any interior cell
 would cost the Solver, where else a camera the layout has could have stood, and the exact greedy
 adversary built camera by camera.
+
+architect_patrol, guard_candidates, guard_placement_scan and greedy_adversary ask the same of the
+guard with heist_plan_place_guard (HeistEnv.plan_place_guard): what one more Architect guard on any
+interior tile would cost the Solver, and the exact greedy adversary under the game's own cost table,
+cameras at 3 points against guards at 5.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -704,14 +709,15 @@ class PlacementScan:
     visibility rows.  Tensors on the tables' device:
     valid [N, M] bool, ticks [N, M] int16, value [N, M] float64, action [N, M] int8 -- PlanPlace's;
     ticks0 [N] int16, value0 [N] float64 -- the baseline: the plan of the base rows alone;
-    cands [N, M, 6] float64 -- the candidates as given."""
+    cands [N, M, 6] float64 -- the candidates as given (a guard_placement_scan's: the tuple of
+    paths, meta and fov)."""
     valid: torch.Tensor
     ticks: torch.Tensor
     value: torch.Tensor
     action: torch.Tensor
     ticks0: torch.Tensor
     value0: torch.Tensor
-    cands: Optional[torch.Tensor] = None
+    cands: Optional[object] = None
 
     def eligible(self) -> torch.Tensor:
         """[N, M] bool: the valid candidates that leave an undetected way to the vault (ticks >= 0).
@@ -748,19 +754,20 @@ class PlacementScan:
         nv = va.sum(1).double()
         return torch.where(nv > 0, blk / nv.clamp(min=1.0), torch.zeros_like(nv))
 
-    def metrics(self) -> dict:
+    def metrics(self, kind: str = "camera") -> dict:
         """The trainer's three figures for this scan (AdversarialTrainer(track_camera_headroom=True)):
         camera_headroom_envs -- the envs that have a best candidate; camera_headroom_mean -- the
         mean headroom over them; camera_blocking_frac -- the mean of blocking() over the envs whose
-        baseline is solvable.  A mean over nothing is 0.0."""
+        baseline is solvable.  A mean over nothing is 0.0.  kind: the keys' prefix ("guard" for a
+        guard_placement_scan, track_guard_headroom's figures)."""
         has = self.best() >= 0
         solv = self.ticks0 >= 0
         z = torch.zeros_like(self.value0)
         s = torch.stack([has.sum().double(), torch.where(has, self.headroom(), z).sum(), solv.sum().double(),
                          torch.where(solv, self.blocking(), z).sum()]).cpu().tolist()
         div = lambda a, b: a / b if b else 0.0  # noqa: E731
-        return {"camera_headroom_mean": div(s[1], s[0]), "camera_blocking_frac": div(s[3], s[2]),
-                "camera_headroom_envs": int(s[0])}
+        return {kind + "_headroom_mean": div(s[1], s[0]), kind + "_blocking_frac": div(s[3], s[2]),
+                kind + "_headroom_envs": int(s[0])}
 
 
 def placement_scan(env, cands, horizon: Optional[int] = None, gamma: float = 1.0, base: Optional[torch.Tensor] = None,
@@ -872,3 +879,216 @@ def greedy_cameras(env, n: int, headings, fov: float, speed: float, vision_range
         env.set_layouts(layouts, budget=budget)
         env.reset()
     return cams_out, pred_out
+
+
+# -- guard placement (heist_plan_place_guard, HeistEnv.plan_place_guard) --------------------------
+
+CAMERA_COST, GUARD_COST = 3, 5   # the Architect's cost table (BUDGET_COSTS; heist_set_layout's purchase)
+_PATROL_OFFS = ((0, 0), (0, 1), (0, 2), (1, 2), (2, 2), (2, 1), (2, 0), (1, 0))
+
+
+def architect_patrol(r: int, c: int, R: int, C: int):
+    """The 8-point rectangle patrol the Architect's decode gives a guard on tile (r, c) of an R x C
+    grid (arch_decode_kernel, networks.py:324-335): the ring of the 3 x 3 block centred on (r, c),
+    clockwise from its top-left tile, every point clamped to the interior.  A list of 8 (row, col)."""
+    return [(max(1, min(R - 2, r + dr - 1)), max(1, min(C - 2, c + dc - 1))) for dr, dc in _PATROL_OFFS]
+
+
+def guard_candidates(grid, speed: int = 1, vision_range: int = 4, fov: float = 90.0):
+    """The Architect's guard (architect_patrol's path, speed 1, range 4, fov 90 by default) on every
+    interior tile, for every env of grid [N, R, C] int8, as heist_plan_place_guard's three arrays:
+    (paths int32 [N, M, 8, 2], meta int32 [N, M, 4] = (len, speed, vision_range, idx 0), fov
+    float64 [N, M, 2] = (fov_angle, heading 0.0)), M = (R - 2)(C - 2), tiles in row-major order, so
+    M and the order are the same for every env.  A tile whose patrol start is not EMPTY in env e
+    carries no candidate there: its len is 0, which the kernel reports as not valid.  Pure torch, on
+    the device of grid."""
+    grid = torch.as_tensor(grid)
+    if grid.dim() != 3 or grid.shape[1] < 3 or grid.shape[2] < 3:
+        raise ValueError("guard_candidates: grid must be [N, R, C] with R, C >= 3")
+    n, R, C = (int(v) for v in grid.shape)
+    dev = grid.device
+    pts = torch.tensor([architect_patrol(r, c, R, C) for r in range(1, R - 1) for c in range(1, C - 1)],
+                       dtype=torch.int32, device=dev)                                   # [M, 8, 2]
+    M = int(pts.shape[0])
+    start = grid[:, pts[:, 0, 0].long(), pts[:, 0, 1].long()]                            # [N, M] the start tiles
+    meta = torch.zeros((n, M, 4), dtype=torch.int32, device=dev)
+    meta[:, :, 0] = torch.where(start == 0, 8, 0).to(torch.int32)
+    meta[:, :, 1] = int(speed)
+    meta[:, :, 2] = int(vision_range)
+    fv = torch.zeros((n, M, 2), dtype=torch.float64, device=dev)
+    fv[:, :, 0] = float(fov)
+    return pts.unsqueeze(0).expand(n, -1, -1, -1).contiguous(), meta, fv
+
+
+def guard_placement_scan(env, cands, horizon: Optional[int] = None, gamma: float = 1.0,
+                         base: Optional[torch.Tensor] = None, max_bytes: int = 1 << 30) -> PlacementScan:
+    """placement_scan for guards: every candidate of cands = (paths, meta, fov) (guard_candidates'
+    arrays, [N, M, ...] or [M, ...]) tried on every env of a HeistEnv as it stands, with
+    HeistEnv.plan_place_guard in the same chunks of M, the rows dropped, the tables concatenated.
+    The baseline ticks0 / value0 is the plan of the base rows alone (a candidate of len 0).
+    PlacementScan's best() / headroom() / blocking() / metrics("guard") read the result.  Reads the
+    envs only."""
+    from .obs_compact import record_words
+    H = min(int(env.config.max_steps), 1024) if horizon is None else int(horizon)
+    pa, me, fv = (x.to(env.device) for x in env._guard_candidates_arg(*cands))
+    M = int(pa.shape[1])
+    if base is None:
+        base = env.plan_field(horizon=H).vis
+    per = 4 * max(H, 1) * env.n_envs * record_words(env.rows, env.cols)
+    step = max(1, int(max_bytes) // per)
+    none = (torch.zeros((1, 1, 2), dtype=torch.int32), torch.zeros((1, 4), dtype=torch.int32),
+            torch.zeros((1, 2), dtype=torch.float64))
+    p0 = env.plan_place_guard(*none, horizon=H, gamma=gamma, base=base)
+    parts = []
+    for m0 in range(0, M, step):
+        pp = env.plan_place_guard(pa[:, m0:m0 + step], me[:, m0:m0 + step], fv[:, m0:m0 + step], horizon=H,
+                                  gamma=gamma, base=base)
+        parts.append((pp.valid, pp.ticks, pp.value, pp.action))
+        del pp
+    valid, ticks, value, action = (torch.cat(x, 1) for x in zip(*parts))
+    return PlacementScan(valid, ticks, value, action, p0.ticks[:, 0], p0.value[:, 0], (pa, me, fv))
+
+
+def greedy_pick(cam_scan: Optional[PlacementScan], guard_scan: Optional[PlacementScan], remaining,
+                cam_ok: Optional[torch.Tensor] = None, guard_ok: Optional[torch.Tensor] = None):
+    """greedy_adversary's selection rule on two scans of the same envs over the same base rows.  Per
+    env, among the candidates that are eligible (valid, the layout stays solvable), affordable (3
+    points for a camera, 5 for a guard, against remaining [N]) and not masked out (cam_ok [N, Mc],
+    guard_ok [N, Mg] bool), the one that takes the most optimal return per budget point, gain =
+    (value0 - value) / cost in float64; only a gain above 0 counts.  Ties go to the camera, then to
+    the lowest index.  Returns (kind [N] int64: 0 camera, 1 guard, -1 none; index [N] int64, -1 for
+    none; gain [N] float64, 0.0 for none)."""
+    ref = cam_scan if cam_scan is not None else guard_scan
+    dev = ref.value0.device
+    remaining = torch.as_tensor(remaining, dtype=torch.int64, device=dev).reshape(-1)
+    n = int(ref.value0.shape[0])
+    best_gain = torch.zeros(n, dtype=torch.float64, device=dev)
+    kind = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    index = torch.full((n,), -1, dtype=torch.int64, device=dev)
+    for k, (sc, cost, ok) in enumerate(((cam_scan, CAMERA_COST, cam_ok), (guard_scan, GUARD_COST, guard_ok))):
+        if sc is None or sc.value.shape[1] == 0:
+            continue
+        el = sc.eligible() & (remaining >= cost).reshape(-1, 1)
+        if ok is not None:
+            el = el & ok.to(dev)
+        # a tensor divisor: one IEEE division on every device (a scalar divisor is multiplied by its reciprocal on the GPU)
+        gain = (sc.value0.reshape(-1, 1) - sc.value) / torch.full_like(sc.value, float(cost))
+        gain = torch.where(el, gain, torch.full_like(gain, -float("inf")))
+        top, arg = gain.max(1)  # the first maximum is not promised by max: take the lowest index by hand
+        m = gain.shape[1]
+        idx = torch.arange(m, device=dev, dtype=torch.int64).reshape(1, m).expand_as(gain)
+        arg = torch.where(gain == top.reshape(-1, 1), idx, torch.full_like(idx, m)).min(1).values
+        take = top > best_gain  # strictly: an equal guard does not displace a camera
+        best_gain = torch.where(take, top, best_gain)
+        kind = torch.where(take, torch.full_like(kind, k), kind)
+        index = torch.where(take, arg, index)
+    return kind, index, best_gain
+
+
+@dataclass
+class GreedyAdversary:
+    """greedy_adversary's output.  Per round r (lists, one entry per round that some env still
+    bought in): kind[r] [N] int64 (0 camera, 1 guard, -1 the env bought nothing), index[r] [N]
+    int64 into that kind's candidates, value[r] [N] float64 -- the Solver's optimal return the scan
+    predicts for the layout with everything bought so far, ticks[r] [N] int16 likewise.
+    cameras[e], guards[e]: what env e bought, in order, as heist_set_layout dicts -- appended to the
+    env's own lists (HeistEnv.layout_lists) they rebuild the adversary's layout at budget spent0[e]
+    + spent[e].  spent [N] int64: the points used.  vis [H, N, W] int32: the final layout's
+    visibility rows."""
+    kind: list
+    index: list
+    value: list
+    ticks: list
+    cameras: list
+    guards: list
+    spent: torch.Tensor
+    vis: torch.Tensor
+
+
+def greedy_adversary(env, budget, camera_cands=None, guard_cands=None, horizon: Optional[int] = None,
+                     gamma: float = 1.0, max_rounds: int = 64, max_bytes: int = 1 << 30) -> GreedyAdversary:
+    """The exact greedy adversary under the game's cost table (camera 3, guard 5), without rebuilding
+    a layout: each round scans camera_cands (camera_candidates' rows or None) and guard_cands
+    (guard_candidates' arrays or None) over the current base rows, takes greedy_pick's choice per env
+    within what is left of budget (an int or [N]), and the chosen variant's visibility rows become
+    the next round's base (one plan_place and one plan_place_guard launch at M = 1).  A candidate on
+    a tile an earlier choice took -- a camera's tile, a guard's start tile -- is no longer offered.
+    The envs should be fresh from set_layout + reset, so that the prediction is the value of the
+    rebuilt layout's first attempt.  Stops when no env buys, or after max_rounds.  Reads the envs
+    only."""
+    dev, n = env.device, env.n_envs
+    H = min(int(env.config.max_steps), 1024) if horizon is None else int(horizon)
+    left = torch.as_tensor(budget, dtype=torch.int64, device=dev).reshape(-1).expand(n).clone()
+    cd = None
+    if camera_cands is not None:
+        cd = torch.as_tensor(camera_cands)
+        cd = (cd.unsqueeze(0).expand(n, -1, -1) if cd.dim() == 2 else cd).to(dev).contiguous()
+    ga = None
+    if guard_cands is not None:
+        ga = tuple(x.to(dev).contiguous() for x in env._guard_candidates_arg(*guard_cands))
+    if cd is None and ga is None:
+        raise ValueError("greedy_adversary: need camera_cands or guard_cands")
+    taken = torch.zeros((n, env.rows, env.cols), dtype=torch.bool, device=dev)
+    ar = torch.arange(n, device=dev)
+
+    def free(r, c):  # [N, M] bool: the candidate's tile is not taken (tiles outside the grid: the kernel rejects them)
+        inside = (r >= 0) & (r < env.rows) & (c >= 0) & (c < env.cols)
+        return ~(taken[ar.reshape(-1, 1), r.clamp(0, env.rows - 1), c.clamp(0, env.cols - 1)] & inside)
+
+    base = env.plan_field(horizon=H).vis
+    out = GreedyAdversary([], [], [], [], [[] for _ in range(n)], [[] for _ in range(n)],
+                          torch.zeros(n, dtype=torch.int64, device=dev), base)
+    for _ in range(int(max_rounds)):
+        cs = gs = c_ok = g_ok = None
+        if cd is not None:
+            cs = placement_scan(env, cd, horizon=H, gamma=gamma, base=base, max_bytes=max_bytes)
+            fin = torch.isfinite(cd[:, :, 0]) & torch.isfinite(cd[:, :, 1]) & (cd[:, :, :2].abs() < 2.0 ** 31).all(-1)
+            rc = torch.where(fin.unsqueeze(-1), cd[:, :, :2], torch.full_like(cd[:, :, :2], -1.0)).long()
+            c_ok = free(rc[..., 0], rc[..., 1])
+        if ga is not None:
+            gs = guard_placement_scan(env, ga, horizon=H, gamma=gamma, base=base, max_bytes=max_bytes)
+            g_ok = free(ga[0][:, :, 0, 0].long(), ga[0][:, :, 0, 1].long())
+        kind, index, _ = greedy_pick(cs, gs, left, c_ok, g_ok)
+        if not bool((kind >= 0).any()):
+            break
+        ref = cs if cs is not None else gs
+        value, ticks = ref.value0.clone(), ref.ticks0.clone()
+        if cd is not None:
+            is_c = kind == 0
+            i1 = torch.where(is_c, index, torch.zeros_like(index))  # an index into the cameras only where one was chosen
+            row = cd.gather(1, i1.reshape(-1, 1, 1).expand(-1, 1, 6))
+            row = torch.where(is_c.reshape(-1, 1, 1), row, torch.full_like(row, float("nan")))
+            pp = env.plan_place(row, horizon=H, gamma=gamma, base=base)
+            base = pp.vis[:, :, 0].contiguous()
+            value, ticks = torch.where(is_c, pp.value[:, 0], value), torch.where(is_c, pp.ticks[:, 0], ticks)
+            for e in torch.nonzero(is_c).reshape(-1).tolist():
+                v = row[e, 0].tolist()
+                out.cameras[e].append({"row": int(v[0]), "col": int(v[1]), "fov_angle": v[2], "heading": v[3],
+                                       "rotation_speed": v[4], "vision_range": int(v[5])})
+                taken[e, int(v[0]), int(v[1])] = True
+        if ga is not None:
+            is_g = kind == 1
+            i1 = torch.where(is_g, index, torch.zeros_like(index))  # likewise: a camera's index can lie past the guards
+            P = ga[0].shape[2]
+            pa = ga[0].gather(1, i1.reshape(-1, 1, 1, 1).expand(-1, 1, P, 2))
+            me = ga[1].gather(1, i1.reshape(-1, 1, 1).expand(-1, 1, 4)).clone()
+            fv = ga[2].gather(1, i1.reshape(-1, 1, 1).expand(-1, 1, 2))
+            me[:, :, 0] = torch.where(is_g.reshape(-1, 1), me[:, :, 0], torch.zeros_like(me[:, :, 0]))
+            pp = env.plan_place_guard(pa, me, fv, horizon=H, gamma=gamma, base=base)
+            base = pp.vis[:, :, 0].contiguous()
+            value, ticks = torch.where(is_g, pp.value[:, 0], value), torch.where(is_g, pp.ticks[:, 0], ticks)
+            for e in torch.nonzero(is_g).reshape(-1).tolist():
+                ln = int(me[e, 0, 0])
+                pts = [(int(r), int(c)) for r, c in pa[e, 0, :ln].tolist()]
+                out.guards[e].append({"patrol_path": pts, "speed": int(me[e, 0, 1]), "vision_range": int(me[e, 0, 2]),
+                                      "fov_angle": float(fv[e, 0, 0])})
+                taken[e, pts[0][0], pts[0][1]] = True
+        cost = torch.where(kind == 0, CAMERA_COST, torch.where(kind == 1, GUARD_COST, 0)).to(torch.int64)
+        left -= cost
+        out.spent += cost
+        out.kind.append(kind)
+        out.index.append(index)
+        out.value.append(value)
+        out.ticks.append(ticks)
+        out.vis = base
+    return out

@@ -161,7 +161,7 @@ class AdversarialTrainer:  # training.py:115-790
                  solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
                  track_optimal: bool = False, track_optimal_return: bool = False,
                  track_emitter_credit: bool = False, track_camera_headroom: bool = False, headroom_envs: int = 64,
-                 headroom_headings: int = 8):
+                 headroom_headings: int = 8, track_guard_headroom: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -238,6 +238,15 @@ class AdversarialTrainer:  # training.py:115-790
             raise ValueError("track_camera_headroom needs headroom_envs >= 1 and headroom_headings >= 1")
         self._camera_headroom = None  # the three metrics of the latest scanned layout batch
         self._headroom_env = None     # the side handle of headroom_envs envs the scan runs on
+        # True: the same envs are scanned for one more guard (search.guard_placement_scan at gamma 1): the
+        # Architect's guard (search.guard_candidates: its decode's 8-point patrol, speed 1, range 4, fov 90) on
+        # every interior tile, and train_iteration reports guard_headroom_mean, guard_blocking_frac and
+        # guard_headroom_envs, track_camera_headroom's figures for the 5-point asset.  False: no launch, no
+        # metric, logs and checkpoints byte-identical
+        self.track_guard_headroom = bool(track_guard_headroom)
+        if self.track_guard_headroom and self.headroom_envs < 1:
+            raise ValueError("track_guard_headroom needs headroom_envs >= 1")
+        self._guard_headroom = None   # the three metrics of the latest scanned layout batch
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -377,6 +386,8 @@ class AdversarialTrainer:  # training.py:115-790
                     self._ablate_layout_batch(good)
                 if self.track_camera_headroom:
                     self._headroom_layout_batch(good)
+                if self.track_guard_headroom:
+                    self._guard_headroom_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
@@ -411,6 +422,16 @@ class AdversarialTrainer:  # training.py:115-790
         from .components.security import Camera
         from .search import PlacementScan, camera_candidates, placement_scan
         ref = Camera(0, 0)
+        side, ids = self._headroom_side(env_ids)
+        hd = [360.0 * h / self.headroom_headings for h in range(self.headroom_headings)]
+        cd = camera_candidates(side.grid_snapshot(), hd, ref.fov_angle, ref.rotation_speed, ref.vision_range)
+        sc = placement_scan(side, cd, gamma=1.0)
+        m = len(ids)
+        self._camera_headroom = PlacementScan(sc.valid[:m], sc.ticks[:m], sc.value[:m], sc.action[:m], sc.ticks0[:m],
+                                              sc.value0[:m]).metrics()
+
+    def _headroom_side(self, env_ids):
+        """The side handle of headroom_envs envs loaded with the first headroom_envs of env_ids, and those ids."""
         ids = [int(e) for e in np.asarray(env_ids, np.int64)[:self.headroom_envs]]
         k = self.headroom_envs
         if self._headroom_env is None:  # a launch plans every env of its handle: the scanned ones get their own
@@ -421,13 +442,18 @@ class AdversarialTrainer:  # training.py:115-790
         # env j of the side handle <- scanned env j mod len(ids): every env holds a layout, the first len(ids) count
         ok = side.load_state(self.env.save_state(ids), index=[j % len(ids) for j in range(k)])
         if not bool(ok.all()):
-            raise RuntimeError("track_camera_headroom: the side handle rejected a saved env")
-        hd = [360.0 * h / self.headroom_headings for h in range(self.headroom_headings)]
-        cd = camera_candidates(side.grid_snapshot(), hd, ref.fov_angle, ref.rotation_speed, ref.vision_range)
-        sc = placement_scan(side, cd, gamma=1.0)
+            raise RuntimeError("track_camera_headroom / track_guard_headroom: the side handle rejected a saved env")
+        return side, ids
+
+    def _guard_headroom_layout_batch(self, env_ids):
+        """The guard headroom of the layouts just set on env_ids (fresh after reset): the first headroom_envs of
+        them, scanned with the Architect's guard on every interior tile."""
+        from .search import PlacementScan, guard_candidates, guard_placement_scan
+        side, ids = self._headroom_side(env_ids)
+        sc = guard_placement_scan(side, guard_candidates(side.grid_snapshot()), gamma=1.0)
         m = len(ids)
-        self._camera_headroom = PlacementScan(sc.valid[:m], sc.ticks[:m], sc.value[:m], sc.action[:m], sc.ticks0[:m],
-                                              sc.value0[:m]).metrics()
+        self._guard_headroom = PlacementScan(sc.valid[:m], sc.ticks[:m], sc.value[:m], sc.action[:m], sc.ticks0[:m],
+                                             sc.value0[:m]).metrics("guard")
 
     def close(self):
         """Release the trainer's env handles: the batch's and, if a scan made one, the camera-headroom side
@@ -779,6 +805,8 @@ class AdversarialTrainer:  # training.py:115-790
             out.update(self._emitter_credit)
         if self.track_camera_headroom and self._camera_headroom is not None:
             out.update(self._camera_headroom)
+        if self.track_guard_headroom and self._guard_headroom is not None:
+            out.update(self._guard_headroom)
         return out
 
     # -- supervised pre-training on exact labels (no reference counterpart) -------------------

@@ -726,6 +726,81 @@ class HeistEnv:
         tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
         return PlanPlace(valid.view(torch.bool), ticks, value, action, vis, tcells, vcells, cd, tick, R, C, float(gamma))
 
+    # -- planner placement for guards (heist_plan_place_guard) ---------------------------------
+    @property
+    def plan_place_guard_supported(self) -> int:
+        """heist_plan_place_guard_supported: 1 when plan_place_guard() has a kernel for this handle
+        (where plan_place() has one)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_place_guard_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_place_guard_supported")
+        return d
+
+    def _guard_candidates_arg(self, paths, meta, fov):
+        """plan_place_guard's three candidate arrays, checked and broadcast to [N, M, ...] (host or
+        device tensors as given; no device is touched)."""
+        n = self.n_envs
+        pa, me, fv = torch.as_tensor(paths), torch.as_tensor(meta), torch.as_tensor(fov)
+        lead = pa.dim() - 2  # 1: [M, ...] for every env, 2: [N, M, ...]
+        if (pa.dtype != torch.int32 or lead not in (1, 2) or pa.shape[-1] != 2 or not 1 <= pa.shape[-2] <= 64
+                or (lead == 2 and pa.shape[0] != n)):
+            raise ValueError("plan_place_guard: paths must be an int32 [%d, M, P, 2] or [M, P, 2] tensor, 1 <= P <= 64" % n)
+        shape = tuple(pa.shape[:lead])
+        if me.dtype != torch.int32 or tuple(me.shape) != shape + (4,):
+            raise ValueError("plan_place_guard: meta must be an int32 %r tensor (len, speed, vision_range, idx)"
+                             % (list(shape) + [4],))
+        if fv.dtype != torch.float64 or tuple(fv.shape) != shape + (2,):
+            raise ValueError("plan_place_guard: fov must be a float64 %r tensor (fov_angle, heading)"
+                             % (list(shape) + [2],))
+        if lead == 1:
+            pa, me, fv = (x.unsqueeze(0).expand(n, *x.shape) for x in (pa, me, fv))
+        return pa, me, fv
+
+    def plan_place_guard(self, paths, meta, fov, horizon: Optional[int] = None, gamma: float = 1.0,
+                         base: Optional[torch.Tensor] = None, cells: bool = False) -> "PlanPlace":
+        """heist_plan_place_guard: every env as it stands planned with one more guard, M candidates
+        per env in one launch that casts the candidate alone -- plan_place's answers over the rows
+        of `base` ORed with the candidate's cone and its own cell.
+        paths: int32 [N, M, P, 2] patrol points (row, col), 1 <= P <= 64; meta: int32 [N, M, 4] =
+        (len, speed, vision_range, idx), idx the patrol index the guard stands on now; fov: float64
+        [N, M, 2] = (fov_angle, heading), the heading it has now -- or [M, ...] each, the same
+        candidates on every env.  base, horizon, gamma, cells as in plan_place.  Returns a PlanPlace
+        whose cands is the tuple (paths, meta, fov) as launched.  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        W = record_words(R, C)
+        pa, me, fv = (x.to(self.device).contiguous() for x in self._guard_candidates_arg(paths, meta, fov))
+        M, P = int(pa.shape[1]), int(pa.shape[2])
+        if base is None:
+            base = self.plan_field(horizon=H).vis if 1 <= H <= 1024 else None
+        elif (not isinstance(base, torch.Tensor) or base.dtype != torch.int32 or tuple(base.shape) != (h, n, W)
+              or base.device != self.device):
+            raise ValueError("plan_place_guard: base must be an int32 [%d, %d, %d] tensor on %s" % (h, n, W, self.device))
+        else:
+            base = base.contiguous()
+            if base.data_ptr() % 16:  # a slice that starts off a 16-byte boundary
+                base = base.clone()
+        kw = dict(device=self.device)
+        valid = torch.empty((n, M), dtype=torch.uint8, **kw)
+        ticks = torch.empty((n, M), dtype=torch.int16, **kw)
+        value = torch.empty((n, M), dtype=torch.float64, **kw)
+        action = torch.empty((n, M), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, M, W), dtype=torch.int32, **kw)
+        tcells = torch.empty((n, M, R, C), dtype=torch.int16, **kw) if cells else None
+        vcells = torch.empty((n, M, R, C), dtype=torch.float64, **kw) if cells else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_place_guard(self._h, H, float(gamma), M, P, nat.ptr(pa) if M else None,
+                                                       nat.ptr(me) if M else None, nat.ptr(fv) if M else None,
+                                                       nat.ptr(base), nat.ptr(valid), nat.ptr(ticks), nat.ptr(value),
+                                                       nat.ptr(action), nat.ptr(vis), nat.ptr(tcells), nat.ptr(vcells),
+                                                       self._stream()),
+                      "heist_plan_place_guard")
+        ex = self.export()
+        tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
+        return PlanPlace(valid.view(torch.bool), ticks, value, action, vis, tcells, vcells, (pa, me, fv), tick, R, C,
+                         float(gamma))
+
     # -- planner Q (heist_plan_q) --------------------------------------------------------------
     PLAN_Q_OUTPUTS = ("q", "value", "best", "optimal", "gap")
 

@@ -46,6 +46,11 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # one candidate per env per pass), then a full placement_scan of 64
                                                  # envs x every interior cell x 8 headings with its headroom, blocking
                                                  # and relocation-rank figures; also written to profiles/plan_place.log
+  python tools/plan_env.py --place-guard [--gamma G]  # the guard placement (heist_plan_place_guard) on the Architect
+                                                 # batch: 8 Architect guards per env next to heist_plan_place with 8
+                                                 # cameras and to the twin-handle route, then a full guard scan of 64
+                                                 # envs with headroom per budget point next to the best camera's; also
+                                                 # written to profiles/plan_place_guard.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -543,6 +548,121 @@ def place_mode(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def place_guard_mode(args, dev):
+    """heist_plan_place_guard on the Architect batch, one JSON line per row, each with its N, M and
+    device seconds per variant: (a) the launch at M = 8 Architect guards per env (the decode's 8-point
+    patrol, speed 1, range 4, fov 90, on a random interior tile each); (b) heist_plan_place in the
+    same process with 8 reference cameras per env; (c) the route without the kernel -- candidate 0 of
+    every env laid into a twin handle with one more guard slot by set_layout_batch + reset +
+    plan_field + plan_value -- with the bitwise-equality flag; (d) a full guard_placement_scan of 64
+    envs x every interior tile, with its headroom and blocking share, and next to it the best
+    camera's headroom, both per budget point (guard 5, camera 3)."""
+    from heist_amd.components.security import Camera
+    from heist_amd.search import (CAMERA_COST, GUARD_COST, architect_patrol, camera_candidates, guard_candidates,
+                                  guard_placement_scan, placement_scan)
+    from heist_amd.vec_env import LayoutBatch
+    H = min(args.horizon or args.max_steps, 1024)
+    N, R, M = args.envs, args.grid, 8
+    ref = Camera(0, 0)
+    env = make_env(args, "architect", dev)
+    kc = env.kernel_config()
+    assert env.plan_place_guard_supported == 1, kc
+    head = {"config": "%dx%d" % (R, R), "layouts": "architect", "horizon": H, "gamma": args.gamma,
+            "multi_waves": kc["multi_waves"], "guard": [1, 4, 90.0]}
+    lines = []
+
+    def emit(row):
+        lines.append(json.dumps(dict(head, **row)))
+        print(lines[-1], flush=True)
+
+    def med(fn, runs=None):
+        ms = timed(dev, fn, args.warmup, runs or args.runs)
+        return statistics.median(ms), ms
+
+    # (a) M = 8 Architect guards per env, each decoded from a random interior tile
+    gen = torch.Generator().manual_seed(args.seed)
+    cell = torch.randint(1, R - 1, (N, M, 2), generator=gen)
+    ring = {(r, c): architect_patrol(r, c, R, R) for r in range(1, R - 1) for c in range(1, R - 1)}
+    pa = torch.tensor([[ring[(int(r), int(c))] for r, c in row] for row in cell.tolist()], dtype=torch.int32).to(dev)
+    me = torch.tensor([8, 1, 4, 0], dtype=torch.int32).reshape(1, 1, 4).expand(N, M, 4).contiguous().to(dev)
+    fv = torch.tensor([90.0, 0.0], dtype=torch.float64).reshape(1, 1, 2).expand(N, M, 2).contiguous().to(dev)
+    base = env.plan_field(H).vis
+    pp = env.plan_place_guard(pa, me, fv, H, gamma=args.gamma, base=base)
+    valid, ticks_a, value_a = pp.valid.clone(), pp.ticks.clone(), pp.value.clone()
+    del pp
+    a, a_ms = med(lambda: env.plan_place_guard(pa, me, fv, H, gamma=args.gamma, base=base))
+    none = torch.zeros_like(me)
+    s, s_ms = med(lambda: env.plan_place_guard(pa, none, fv, H, gamma=args.gamma, base=base))
+    emit({"row": "a", "what": "plan_place_guard", "envs": N, "M": M, "valid_frac": float(valid.float().mean()),
+          "launch_ms_median": a, "launch_ms": a_ms, "seconds_per_variant": a * 1e-3 / (N * M),
+          "invalid_candidates_launch_ms_median": s, "invalid_candidates_launch_ms": s_ms,
+          "sweeps_and_copy_seconds_per_variant": s * 1e-3 / (N * M),
+          "forward_seconds_per_variant": (a - s) * 1e-3 / (N * M)})
+
+    # (b) plan_place in the same process: the reference camera on the same tiles, heading 45 m
+    cd = torch.cat([cell.double(), torch.full((N, M, 1), ref.fov_angle, dtype=torch.float64),
+                    (45.0 * torch.arange(M, dtype=torch.float64)).reshape(1, M, 1).expand(N, M, 1),
+                    torch.full((N, M, 1), ref.rotation_speed, dtype=torch.float64),
+                    torch.full((N, M, 1), float(ref.vision_range), dtype=torch.float64)], 2).to(dev)
+    b, b_ms = med(lambda: env.plan_place(cd, H, gamma=args.gamma, base=base))
+    emit({"row": "b", "what": "plan_place, 8 reference cameras per env", "envs": N, "M": M, "launch_ms_median": b,
+          "launch_ms": b_ms, "seconds_per_variant": b * 1e-3 / (N * M), "guard_over_camera": a / b})
+
+    # (c) the route without the kernel: candidate 0 of every env as a guard of a twin's layout
+    layouts, spent = env.layout_lists()
+    plus = [(w, cams, g + [{"patrol_path": ring[(int(rc[0]), int(rc[1]))], "speed": 1, "vision_range": 4,
+                            "fov_angle": 90.0}]) for (w, cams, g), rc in zip(layouts, cell[:, 0].tolist())]
+    twin = HeistEnv(N, env.config, max_cams=env.max_cams, max_guards=env.max_guards + 1, max_path=env.max_path,
+                    device=dev, auto_reset=True)
+    lb = LayoutBatch.from_lists(plus, [sp + GUARD_COST for sp in spent], twin.max_cams, twin.max_guards, twin.max_path,
+                                dev, R, R)
+    sr, sc = env.config.start_pos
+
+    def route():
+        twin.set_layout_batch(lb)
+        twin.reset()
+        return twin.plan_field(H), twin.plan_value(H, gamma=args.gamma)
+
+    pf, pv = route()
+    v0 = valid[:, 0]
+    same = bool(torch.equal(pf.togo[:, sr, sc][v0], ticks_a[:, 0][v0])
+                and torch.equal(pv.value[:, sr, sc][v0].contiguous().view(torch.int64),
+                                value_a[:, 0][v0].contiguous().view(torch.int64)))
+    del pf, pv
+    c, c_ms = med(route)
+    emit({"row": "c", "what": "set_layout_batch + reset + plan_field + plan_value on a twin handle", "envs": N, "M": 1,
+          "twin_equals_plan_place_guard_bitwise_on_valid_candidates": same,
+          "pass_ms_median": c, "pass_ms": c_ms, "seconds_per_variant": c * 1e-3 / N, "route_over_place_guard": (c / N) / (a / (N * M))})
+    twin.close()
+
+    # (d) a full scan: 64 envs, the Architect's guard on every interior tile; the best camera next to it
+    n = min(64, N)
+    side = HeistEnv(n, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                    auto_reset=True)
+    assert bool(side.load_state(env.save_state(list(range(n)))).all())
+    grid = side.grid_snapshot()
+    full = guard_candidates(grid)
+    scan = guard_placement_scan(side, full, H, gamma=args.gamma)
+    d, d_ms = med(lambda: guard_placement_scan(side, full, H, gamma=args.gamma), runs=min(args.runs, 3))
+    cams = placement_scan(side, camera_candidates(grid, [45.0 * h for h in range(8)], ref.fov_angle, ref.rotation_speed,
+                                                  ref.vision_range), H, gamma=args.gamma)
+    Mf = int(full[0].shape[1])
+    gm, cm = scan.metrics("guard"), cams.metrics("camera")
+    emit({"row": "d", "what": "guard_placement_scan, every interior tile", "envs": n, "M": Mf,
+          "scan_ms_median": d, "scan_ms": d_ms, "seconds_per_variant": d * 1e-3 / (n * Mf),
+          "valid_frac": float(scan.valid.float().mean()), "solvable_baselines": int((scan.ticks0 >= 0).sum()), **gm,
+          "headroom_max": float(scan.headroom().max()), "blocking_frac_max": float(scan.blocking().max()),
+          "guard_headroom_per_point": gm["guard_headroom_mean"] / GUARD_COST, **cm,
+          "camera_headroom_per_point": cm["camera_headroom_mean"] / CAMERA_COST})
+    side.close()
+    env.close()
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_place_guard.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --place-guard --gamma %r\n" % args.gamma)
+        fh.write("\n".join(lines) + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -573,12 +693,17 @@ def main(argv=None):
                     "M x (heist_plan_field + heist_plan_value) on all three batches, with the critical / redundant emitters")
     ap.add_argument("--place", action="store_true", help="time heist_plan_place next to heist_plan_masked and to the "
                     "twin-handle route on the Architect batch, then a full placement_scan of 64 envs")
+    ap.add_argument("--place-guard", action="store_true", help="time heist_plan_place_guard next to heist_plan_place "
+                    "and to the twin-handle route on the Architect batch, then a full guard_placement_scan of 64 envs "
+                    "(log: profiles/plan_place_guard.log)")
     ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
                     "profiles/plan_play.log, --q's: profiles/plan_q.log, --ablate's: profiles/plan_masked.log, --place's: "
                     "profiles/plan_place.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.place_guard:
+        return place_guard_mode(args, dev)
     if args.place:
         return place_mode(args, dev)
     if args.ablate:
