@@ -550,6 +550,70 @@ int heist_plan_place_guard(heist_t h, int horizon, double gamma, int M, int P, c
                            uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
                            heist_stream_t stream);
 
+/* Planner walls, no reference counterpart: heist_plan_masked's two answers for every env with walls
+ * added or removed -- M variants per env in one launch, which tells which wall a layout's difficulty
+ * is due to, which wall the Solver hides behind, where one more wall would have mattered and whether
+ * a wall keeps the level valid.  This is the case the three what-ifs above exclude: a wall stops
+ * rays and moves, so a variant's visibility is no union over rows that already exist and its effect
+ * is not monotone (a wall can help the Solver, and taking one away can hurt it).  Every variant is
+ * therefore cast in full against its own edited stop map, and both recurrences run on its own
+ * edited tile grid.
+ *   edits        [N][M][E][3] int32, 4-byte aligned, 1 <= E <= 8: edit i of variant (e, m) is (row,
+ *                col, op); op 0 is no edit (row and col are ignored), 1 adds a wall, 2 removes one.
+ *   emitter_mask [N][M] uint64, 8-byte aligned, or NULL (every slot live): heist_plan_masked's mask
+ *                with heist_plan_masked's meaning, so that "this camera off, a wall here" -- a camera
+ *                moved behind a new wall, with heist_plan_place on top -- is one variant.
+ * Every edit with op != 0 is judged against env e's grid as it stands, not as the variant's earlier
+ * edits would leave it, and every comparison is decided before a byte is indexed:
+ *   add (op 1):    valid iff 0 < r < R-1, 0 < c < C-1, tile (r, c) is EMPTY and it is not the Solver's
+ *                  current cell (environment.py:160-167): not a wall, the start, the vault, a camera
+ *                  or a guard's start tile.
+ *   remove (op 2): valid iff 0 < r < R-1, 0 < c < C-1 and tile (r, c) is WALL.  The border stays; a
+ *                  wall that a guard's start tile replaced is kGuard and cannot be removed.
+ *   any other op:  invalid.
+ * Variant (e, m) is valid iff every one of its edits with op != 0 is valid and no two of them name
+ * the same tile.  No int32 pattern in edits makes the launch read or write out of bounds.
+ *   valid_out [N][M] uint8: 1 for a valid variant, else 0 (whatever HK is).
+ * An invalid variant is planned with no edit at all, under its mask: it is heist_plan_masked's
+ * variant.  A valid variant is planned from env e's current state exactly as heist_plan_masked plans
+ * one, HK = min(horizon, max_steps - tick[e]) ticks (0 for an env already done), on the edited tile
+ * grid -- an added tile is WALL, a removed one EMPTY -- which is both the stop map the rays march
+ * against and the grid the two backward sweeps read.  Every emitter record advances as in
+ * heist_plan_masked.  Every live guard is raycast live in every variant, whether or not the handle
+ * caches guard cones: a cone cached for the unedited walls is not the variant's.  A guard whose
+ * patrol crosses an added wall walks onto it, marks its own cell there and casts from there, as an
+ * env guard on a wall tile does.
+ *   level_out [N][M] uint8: 1 iff the variant's grid (the unedited one for an invalid variant) still
+ *             has a 4-neighbour path of non-WALL tiles from the handle's start tile -- not the
+ *             Solver's cell -- to the vault: heist_bfs_valid's answer on that grid.  Where it is 0,
+ *             HeistEnvironment.set_layout would have rejected the level; the variant is planned all
+ *             the same (its ticks are -1 wherever the Solver is cut off).
+ *   ticks_out, value_out, action_out, vis_out [horizon][N][M][W], togo_cells_out, value_cells_out:
+ *             heist_plan_masked's outputs of the same names, shapes, alignments, padding and HK = 0
+ *             fill (-1 / 0.0 / -1, rows k > HK and pad words 0), in heist_plan_masked's arithmetic
+ *             (the same lines in the same order, each one IEEE double operation, none contracted,
+ *             the first maximum under a strict greater-than).  In the cell tables an added wall cell
+ *             holds -1 / 0.0 and a removed one a real value.
+ * A variant with no edit of op != 0 is heist_plan_masked under the same mask, bit for bit, whether
+ * or not the handle caches guard cones.  A valid variant with level_out 1 and every slot live is
+ * heist_plan_field / heist_plan_value, bit for bit, on a handle built from the same layout with its
+ * wall list edited -- the added tiles appended, the removed ones dropped, a budget that still buys
+ * every asset -- and brought to the same state.
+ * The launch only reads the env.
+ * heist_plan_walls_supported: heist_plan_masked_supported's value (the kernel's LDS is
+ *   heist_plan_masked's): every grid up to 32 x 32 at 1, 2 and 4 K-tick waves; 64 x 64 is not
+ *   supported.  -1 on a bad handle.
+ * HEIST_EINVAL: horizon outside 1..1024, gamma not finite or outside [0, 1], M < 1 or N M >= 2^31,
+ * E outside 1..8, a NULL edits, valid_out, level_out, ticks_out, value_out, action_out or vis_out,
+ * vis_out not 16-byte aligned, emitter_mask, value_out or value_cells_out not 8-byte aligned, edits
+ * not 4-byte aligned, ticks_out or togo_cells_out not 2-byte aligned, a probe mode armed
+ * (HEIST_PROBE_MODE), heist_plan_walls_supported 0. */
+int heist_plan_walls_supported(heist_t h);
+int heist_plan_walls(heist_t h, int horizon, double gamma, int M, int E, const int32_t* edits,
+                     const uint64_t* emitter_mask, uint8_t* valid_out, uint8_t* level_out,
+                     int16_t* ticks_out, double* value_out, int8_t* action_out, uint32_t* vis_out,
+                     int16_t* togo_cells_out, double* value_cells_out, heist_stream_t stream);
+
 /* Planner playout, no reference counterpart: one episode per env played from a planner's per-tick
  * tables -- the table's own (expert) play, or that play perturbed on a counter-hashed share of the
  * steps, every visited state still labelled by the table.  The emitters do not depend on the

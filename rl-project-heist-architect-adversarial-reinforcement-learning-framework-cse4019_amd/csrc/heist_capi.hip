@@ -40,6 +40,10 @@ hipError_t launch_plan_value(const EnvParams& p, int horizon, double gamma, doub
 hipError_t launch_plan_masked(const EnvParams& p, int horizon, double gamma, int M, const uint64_t* emitter_mask,
                               int16_t* ticks_out, double* value_out, int8_t* action_out, uint32_t* vis_out,
                               int16_t* togo_cells_out, double* value_cells_out, hipStream_t st);
+hipError_t launch_plan_walls(const EnvParams& p, int horizon, double gamma, int M, int E, const int32_t* edits,
+                             const uint64_t* emitter_mask, uint8_t* valid_out, uint8_t* level_out, int16_t* ticks_out,
+                             double* value_out, int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                             double* value_cells_out, hipStream_t st);
 hipError_t launch_plan_place(const EnvParams& p, int horizon, double gamma, int M, const double* cand,
                              const uint32_t* base_vis, uint8_t* valid_out, int16_t* ticks_out, double* value_out,
                              int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out, double* value_cells_out,
@@ -745,6 +749,41 @@ int heist_plan_place_guard(heist_t h, int horizon, double gamma, int M, int P, c
                                                   valid_out, ticks_out, value_out, action_out, vis_out, togo_cells_out,
                                                   value_cells_out, (hipStream_t)stream),
                    "heist_plan_place_guard");
+}
+
+int heist_plan_walls_supported(heist_t h) { return heist_plan_masked_supported(h); }
+
+int heist_plan_walls(heist_t h, int horizon, double gamma, int M, int E, const int32_t* edits,
+                     const uint64_t* emitter_mask, uint8_t* valid_out, uint8_t* level_out, int16_t* ticks_out,
+                     double* value_out, int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                     double* value_cells_out, heist_stream_t stream) {
+  if (int rc = check_handle(h)) return rc;
+  HEIST_REQUIRE(horizon >= 1 && horizon <= 1024, "heist_plan_walls: need 1 <= horizon <= 1024");
+  HEIST_REQUIRE(std::isfinite(gamma) && gamma >= 0.0 && gamma <= 1.0, "heist_plan_walls: need 0 <= gamma <= 1");
+  HEIST_REQUIRE(M >= 1 && (int64_t)h->p.n_envs * (int64_t)M <= 0x7fffffffll,
+                "heist_plan_walls: need M >= 1 and N * M < 2^31");
+  HEIST_REQUIRE(E >= 1 && E <= 8, "heist_plan_walls: need 1 <= E <= 8");
+  HEIST_REQUIRE(edits && valid_out && level_out && ticks_out && value_out && action_out && vis_out,
+                "heist_plan_walls: null edits or output");
+  HEIST_REQUIRE(((uintptr_t)vis_out & 15) == 0, "heist_plan_walls: vis_out must be 16-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)emitter_mask & 7) == 0 && ((uintptr_t)value_out & 7) == 0 &&
+                    ((uintptr_t)value_cells_out & 7) == 0,
+                "heist_plan_walls: emitter_mask / value_out / value_cells_out must be 8-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)edits & 3) == 0, "heist_plan_walls: edits must be 4-byte aligned");
+  HEIST_REQUIRE(((uintptr_t)ticks_out & 1) == 0 && ((uintptr_t)togo_cells_out & 1) == 0,
+                "heist_plan_walls: ticks_out / togo_cells_out misaligned");
+  HEIST_REQUIRE(h->p.probe_mode == 0, "heist_plan_walls: a probe mode is armed (HEIST_PROBE_MODE)");
+  HEIST_REQUIRE(heist::plan_value_variant_exists(h->p), "heist_plan_walls: no walls kernel for this handle "
+                                                        "(heist_plan_walls_supported is 0)");
+  // the launch's own EnvParams, as heist_plan_masked's: no shared fan (every camera cast live)
+  EnvParams q = h->p;
+  q.fan_on = 0;
+  q.fan_fill = 0;
+  q.fan_base = 0;
+  return check_hip(heist::launch_plan_walls(q, horizon, gamma, M, E, edits, emitter_mask, valid_out, level_out,
+                                            ticks_out, value_out, action_out, vis_out, togo_cells_out,
+                                            value_cells_out, (hipStream_t)stream),
+                   "heist_plan_walls");
 }
 
 int heist_plan_play(heist_t h, int horizon, const int8_t* action_table, const uint32_t* vis, const double* value_table,

@@ -3277,6 +3277,334 @@ __global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ
 }
 
 // ---------------------------------------------------------------------------
+// Planner walls (heist_plan_walls): ticks and return with walls added or removed
+// ---------------------------------------------------------------------------
+//
+// plan_masked_kernel's question for M variants of every env, variant (e, m) being the env with the
+// NE tile edits edits[e][m] applied -- a wall added, a wall removed -- under the emitter slots of
+// emitter_mask[e][m] (include/heist.h).  A wall stops rays and moves, so this is the one what-if
+// that is no union over rows the project already has: the variant's stop map and tile grid are
+// edited in LDS after the prefetch, every ray of every live emitter is marched against the edited
+// map, and both backward sweeps read the edited grid.  Nothing else in LDS depends on walls
+// (cast_rays<NT, D, false, true> reads L.wall alone).  One workgroup per (env, variant), block b =
+// order entry b / M, variant b % M, as plan_masked_kernel.
+// Edits: wave 0 judges the NE edits against the grid as prefetched (the words are the same in every
+// lane; every comparison is made before a byte is indexed), and lane 0 applies them only if all
+// hold, so an invalid variant is plan_masked_kernel's.  Wave 0 then floods the edited grid from the
+// handle's start tile (bfs_wave, set_layout_kernel's row masks) for level_out.
+// Guards: a cone cached for the unedited walls is not the variant's, so every guard record gets
+// hslot = nslot = kUncached on its way into LDS and takes plan_masked_kernel's live branch (the
+// heading in HBM is current for a cached guard too: every env kernel's epilogue writes it).  The
+// guard plane is cleared with the ray plane, as the planners' tick does, and never stamped or read.
+// Forward pass and backward passes: plan_masked_kernel's (a copy: each planner's instances keep
+// their registers), the LDS is plan_value_lds.
+__device__ bool bfs_wave(uint64_t pass, int sr, int sc, int gr, int gc);  // defined with set_layout_kernel
+
+template <int W, int D>
+__global__ __launch_bounds__(64 * W) __attribute__((amdgpu_waves_per_eu(plan_occ(W)))) void plan_walls_kernel(
+    EnvParams p, int H, double gamma, int M, int NE, const int32_t* __restrict__ edits,
+    const uint64_t* __restrict__ emitter_mask, uint8_t* __restrict__ valid_out, uint8_t* __restrict__ level_out,
+    int16_t* __restrict__ ticks_out, double* __restrict__ value_out, int8_t* __restrict__ action_out,
+    uint32_t* vis_out, int16_t* __restrict__ togo_cells_out, double* __restrict__ value_cells_out) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  constexpr int NT = 64 * W;
+  constexpr uint32_t kNone = 0xFFFFu;
+  const int oi = uni((int)(blockIdx.x / (uint32_t)M)), var = uni((int)blockIdx.x - oi * M);
+  const int e = p.dispatch_order ? (p.order[oi] & kOrderEnvMask) : oi;
+  const int t = threadIdx.x;
+  const int lane = t & 63, wave = uni(t >> 6);
+  const bool w0 = wave == 0;
+  const int RC = p.RC, C = p.C;
+  const size_t NM = (size_t)p.n_envs * (size_t)M, em = (size_t)e * (size_t)M + (size_t)var;  // rows per tick, this row
+  const int mc = p.max_cams, mg = p.max_guards, n_slot = mc + mg;
+  const int path_words = mg * p.max_path;
+  const EnvLds L = carve<D>(smem, p.R, p.C, n_slot, path_words, W, mg);
+  EmitterRaw* rec = reinterpret_cast<EmitterRaw*>(
+      smem + align16(env_lds_bytes(p.R, p.C, n_slot, path_words, D, W, mg)));  // [n_slot] records
+  uint8_t* gvis = reinterpret_cast<uint8_t*>(rec + n_slot);  // the guard plane: cleared, never stamped
+  TieBuckets* tb = reinterpret_cast<TieBuckets*>(gvis + D);
+  float2* uq = reinterpret_cast<float2*>(reinterpret_cast<unsigned char*>(tb) + align16(sizeof(TieBuckets)));
+  const int n_chunk = (RC + 63) >> 6;
+  const int nvis = (RC + 31) >> 5, WR = (nvis + 4) & ~3;  // the record's words (obs_record_words)
+  double* val = reinterpret_cast<double*>(uq + 128 * W);           // [2][RC] values, tick parity (16-byte aligned)
+  uint16_t* togo = reinterpret_cast<uint16_t*>(val);               // [2][RC] ticks to go, over val's first array
+  uint32_t* vrow = reinterpret_cast<uint32_t*>(val + 2 * RC);      // [2][nvis] visibility rows, tick parity
+  const EnvBase eb = env_base(p, e);
+
+  {
+    EmitterRaw raw;
+    prefetch<NT>(p, e, eb, L, raw);
+    if (t >= mc) {  // a guard's slot: cast live, whatever the handle caches (the cone is the unedited walls')
+      Guard gd = as_guard(raw);
+      gd.hslot = kUncached;
+      gd.nslot = kUncached;
+      raw = __builtin_bit_cast(EmitterRaw, gd);
+    }
+    if (t < n_slot) rec[t] = raw;
+  }
+  for (int i = t; i < path_words; i += NT) L.path[i] = eb.paths[i];
+  for (int i = t; i < (int)sizeof(TieBuckets) / 4; i += NT)
+    reinterpret_cast<uint32_t*>(tb)[i] = reinterpret_cast<const uint32_t*>(&kTieBuckets_)[i];
+  const EnvScalars s = p.scal[e];
+  const int tick0 = uni(s.tick);
+  int HK = p.max_steps - tick0;
+  HK = HK < H ? HK : H;
+  if (uni(s.done) || HK < 0) HK = 0;
+  const int g = t - mc;
+  const bool live_cam = t < s.n_cams, live_guard = g >= 0 && g < s.n_guards;
+  // slot t is live in this variant (n_slot <= kMaxEmitters = 64: bits from 64 up do not exist)
+  const uint64_t emask = emitter_mask ? emitter_mask[em] : ~0ull;
+  const bool on = t < n_slot && ((emask >> (t & 63)) & 1ull) != 0ull;
+  __syncthreads();  // records, grid and stop map in LDS
+
+  // ---- the variant's edits (include/heist.h): judged by wave 0 against the grid as it stands, applied by
+  // its lane 0 only if every one holds; no other wave touches the grid or the stop map before the barrier
+  const int R = p.R;
+  const int32_t* ed = edits + em * (size_t)NE * 3;
+  bool valid = true;
+  if (w0) {
+    const int pr = uni(s.pos_r), pc = uni(s.pos_c);
+    for (int i = 0; i < NE; ++i) {
+      const int r = uni(ed[3 * i]), c = uni(ed[3 * i + 1]), op = uni(ed[3 * i + 2]);
+      if (op == 0) continue;
+      // interior first (environment.py:160-167): only then is r C + c an index
+      bool ok = (op == 1 || op == 2) && r > 0 && r < R - 1 && c > 0 && c < C - 1;
+      if (ok) {
+        const uint8_t tile = L.grid[r * C + c];
+        ok = op == 1 ? (tile == kEmpty && !(r == pr && c == pc)) : tile == kWall;
+      }
+      for (int j = 0; j < i; ++j)  // no two edits of a variant name one tile
+        if (uni(ed[3 * j + 2]) != 0 && uni(ed[3 * j]) == r && uni(ed[3 * j + 1]) == c) ok = false;
+      valid = valid && ok;
+    }
+    if (valid && lane == 0) {
+      for (int i = 0; i < NE; ++i) {
+        const int r = ed[3 * i], c = ed[3 * i + 1], op = ed[3 * i + 2];
+        if (op == 0) continue;
+        L.grid[r * C + c] = op == 1 ? kWall : kEmpty;
+        L.wall[L.at(r, c)] = op == 1 ? 1 : 0;  // build_wall_map's byte of tile (r, c)
+      }
+    }
+  }
+  __syncthreads();  // the edited grid and stop map, before the flood and the first cast
+  if (w0) {
+    // set_layout_kernel's row masks and flood, on the variant's grid, from the handle's start tile (R <= 64)
+    uint64_t m = 0;
+    if (lane < R)
+      for (int c = 0; c < C; ++c)
+        if (L.grid[lane * C + c] != kWall) m |= 1ull << c;
+    const bool level = bfs_wave(m, p.sr, p.sc, p.vr, p.vc);
+    if (lane == 0) {
+      valid_out[em] = valid ? 1 : 0;
+      level_out[em] = level ? 1 : 0;
+    }
+  }
+
+  // cell / C as a multiply-shift (plan_kernel)
+  const uint32_t cdiv = ((1u << 20) + (uint32_t)C - 1u) / (uint32_t)C;
+
+  // ---- forward: vis_1 .. vis_HK into the variant's rows of vis_out (plan_masked_kernel's live emitters)
+  for (int k = 1; k <= HK; ++k) {
+    // (the barrier that closed the previous tick's pack also closed its readers of vis / em)
+    Emit E;
+    E.kind = -1;
+    if (w0) {
+      // cameras rotate, guards patrol (security.py:49-51, :145-159), unconditionally
+      if (live_cam) {
+        Cam cm = as_cam(rec[t]);
+        cm.heading = py_mod360(cm.heading + cm.speed * 1.0);
+        rec[t] = __builtin_bit_cast(EmitterRaw, cm);
+        E = cam_emit(cm);
+      } else if (live_guard) {
+        Guard gd = as_guard(rec[t]);
+        const bool moves = gd.len >= 2;
+        int nidx = gd.idx;
+        if (moves) {
+          nidx += gd.step;
+          if (nidx >= gd.len) nidx -= gd.len;
+        }
+        const uint16_t np = moves ? L.path[__umul24((uint32_t)g, (uint32_t)p.max_path) + (uint32_t)nidx] : gd.pos;
+        if (moves) {
+          gd.heading = guard_heading_after(p, unpack_r(np) - unpack_r(gd.pos), unpack_c(np) - unpack_c(gd.pos),
+                                           gd.heading);
+        }
+        gd.idx = (int16_t)nidx;
+        gd.pos = np;
+        rec[t] = __builtin_bit_cast(EmitterRaw, gd);
+        E = guard_emit(gd);  // kind 1: hslot is kUncached
+      }
+      if (!on) E.kind = -1;  // switched off: no ray chunk, no own-cell mark, no group
+      publish_emitters(L, E, n_slot);
+    }
+    clear_planes<NT>(p, L, gvis, true);
+    __syncthreads();  // emitter table, cleared planes
+    if (live_guard && E.kind == 1) L.vis[L.at(E.row, E.col)] = 1;  // visibility.py:59
+    cast_rays<NT, D, false, true>(smem, L, p.ray_mode, 0, p.half_deg, tb, uq);
+    __syncthreads();  // plane complete
+
+    // the tick's plane, 64 cells per ballot, as the two words of its chunk; the pad words are 0
+    uint32_t* row = vis_out + ((size_t)(k - 1) * NM + em) * WR;
+    for (int ch = wave; ch < n_chunk; ch += W) {
+      const int cell = 64 * ch + lane;
+      bool seen = false;
+      if (cell < RC) {
+        const int r = (int)(((uint32_t)cell * cdiv) >> 20), c = cell - r * C;
+        seen = L.vis[L.at(r, c)] != 0;
+      }
+      const unsigned long long m = __ballot(seen);
+      if (lane < 2 && 2 * ch + lane < WR) row[2 * ch + lane] = (uint32_t)(m >> (32 * lane));
+    }
+    for (int i = 2 * n_chunk + t; i < WR; i += NT) row[i] = 0u;
+    __syncthreads();  // the plane's readers are done
+  }
+
+  // the rows this variant did not run, 16 bytes per store (WR is a multiple of 4, vis_out 16-byte aligned)
+  {
+    const int q4 = WR >> 2;
+    const uint4 z = make_uint4(0u, 0u, 0u, 0u);
+    for (int i = t; i < (H - HK) * q4; i += NT) {
+      const int r = HK + i / q4, q = i - (i / q4) * q4;
+      reinterpret_cast<uint4*>(vis_out + ((size_t)r * NM + em) * WR)[q] = z;
+    }
+  }
+  if (HK == 0) {  // block-uniform: an env already done (or past max_steps) has no plan and collects nothing
+    if (t == 0) {
+      ticks_out[em] = (int16_t)-1;
+      value_out[em] = 0.0;
+      action_out[em] = (int8_t)-1;
+    }
+    for (int x = t; x < RC; x += NT) {
+      if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)-1;
+      if (value_cells_out) value_cells_out[em * RC + x] = 0.0;
+    }
+    return;
+  }
+
+  // row k of vis_out is vis_{k+1}; nvis <= NT for every instance (plan_value_variant_exists, which launch_plan_walls requires)
+  auto load_row = [&](int k) {
+    return __hip_atomic_load(vis_out + ((size_t)k * NM + em) * WR + (t < nvis ? t : 0), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_AGENT);
+  };
+  const int vr = p.vr, vc = p.vc, vcell = vr * C + vc;
+  const int pcell = uni(s.pos_r) * C + uni(s.pos_c);  // the Solver's cell
+
+  // ---- backward, ticks: togo_{HK-1} .. togo_0 (plan_masked_kernel's sweep) on the edited grid
+  __threadfence();  // this variant's rows visible to the lanes that read them back
+  for (int x = t; x < RC; x += NT) togo[(HK & 1) * RC + x] = (uint16_t)kNone;  // togo_HK
+  __syncthreads();
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;          // vis_{k+1}
+    const uint16_t* nxt = togo + ((k + 1) & 1) * RC;     // togo_{k+1}
+    uint16_t* cur = togo + (k & 1) * RC;                 // togo_k
+    for (int x = t; x < RC; x += NT) {
+      uint32_t best = kNone;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        auto tg = [&](int y) -> uint32_t {
+          if ((vk[y >> 5] >> (y & 31)) & 1u) return kNone;
+          if (y == vcell) return 1u;
+          const uint32_t v = nxt[y];
+          return v == kNone ? kNone : v + 1u;
+        };
+        auto moved = [&](bool inside, int y) { return inside && L.grid[y] != kWall ? y : x; };
+        best = tg(x);
+        uint32_t v = tg(moved(r > 0, x - C));
+        if (v < best) best = v;
+        v = tg(moved(r + 1 < p.R, x + C));
+        if (v < best) best = v;
+        v = tg(moved(c > 0, x - 1));
+        if (v < best) best = v;
+        v = tg(moved(c + 1 < C, x + 1));
+        if (v < best) best = v;
+      }
+      cur[x] = (uint16_t)best;
+      if (k == 0) {
+        if (togo_cells_out) togo_cells_out[em * RC + x] = (int16_t)(uint16_t)best;
+        if (x == pcell) ticks_out[em] = (int16_t)(uint16_t)best;
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // togo_k and vis_k complete; their previous holders' readers are done
+  }
+
+  // ---- backward, return: V_{HK-1} .. V_0 (plan_masked_kernel's sweep) over the same rows; the
+  // barrier above closed the last readers of togo and of both visibility rows
+  for (int x = t; x < RC; x += NT) val[(HK & 1) * RC + x] = 0.0;  // V_HK
+  {
+    const uint32_t w = load_row(HK - 1);
+    if (t < nvis) vrow[((HK - 1) & 1) * nvis + t] = w;
+  }
+  __syncthreads();
+  const int D0 = uni(s.initial_dist);
+  const bool bonus = D0 > 3;
+  const double r_step = p.r_step, r_detect = p.r_detect, r_vault = p.r_vault;
+  for (int k = HK - 1; k >= 0; --k) {
+    uint32_t ahead = 0u;
+    if (k > 0) ahead = load_row(k - 1);  // vis_k, for the next step
+    const uint32_t* vk = vrow + (k & 1) * nvis;        // vis_{k+1}
+    const double* nxt = val + ((k + 1) & 1) * RC;      // V_{k+1}
+    double* cur = val + (k & 1) * RC;                  // V_k
+    const bool last = tick0 + k + 1 >= p.max_steps;    // the env times out on this tick (k = HK - 1 only)
+    for (int x = t; x < RC; x += NT) {
+      double best = 0.0;
+      int act = -1;
+      if (L.grid[x] != kWall) {
+        const int r = (int)(((uint32_t)x * cdiv) >> 20), c = x - r * C;
+        const int dx = iabs_(r - vr) + iabs_(c - vc);
+        // q of the move to cell y = (yr, yc): step_multi_body's reward in its order, then the tail
+        auto q = [&](int y, int yr, int yc) -> double {
+          const int curr = iabs_(yr - vr) + iabs_(yc - vc);
+          double rew = r_step;
+          rew += (double)(dx - curr) * 0.1;
+          if (curr <= 3 && bonus) rew += 0.05 * (double)(3 - curr);
+          const bool seen = ((vk[y >> 5] >> (y & 31)) & 1u) != 0u;
+          if (seen) rew += r_detect;
+          if (y == vcell) rew += r_vault;
+          if (last) {
+            double frac = 1.0 - (double)curr / (double)(D0 > 1 ? D0 : 1);
+            if (frac < 0.0) frac = 0.0;
+            rew += frac * 2.0;
+          }
+          const double on_ = rew + gamma * nxt[y];
+          return (seen || y == vcell || last) ? rew : on_;
+        };
+        best = q(x, r, c);
+        act = 0;
+        bool ok = r > 0 && L.grid[x - C] != kWall;
+        double v = ok ? q(x - C, r - 1, c) : best;
+        if (v > best) best = v, act = 1;
+        ok = r + 1 < p.R && L.grid[x + C] != kWall;
+        v = ok ? q(x + C, r + 1, c) : best;
+        if (v > best) best = v, act = 2;
+        ok = c > 0 && L.grid[x - 1] != kWall;
+        v = ok ? q(x - 1, r, c - 1) : best;
+        if (v > best) best = v, act = 3;
+        ok = c + 1 < C && L.grid[x + 1] != kWall;
+        v = ok ? q(x + 1, r, c + 1) : best;
+        if (v > best) best = v, act = 4;
+      }
+      cur[x] = best;
+      if (k == 0) {
+        if (value_cells_out) value_cells_out[em * RC + x] = best;
+        if (x == pcell) {
+          value_out[em] = best;
+          action_out[em] = (int8_t)act;
+        }
+      }
+    }
+    if (k > 0 && t < nvis) vrow[((k - 1) & 1) * nvis + t] = ahead;
+    __syncthreads();  // V_k and vis_k complete; their previous holders' readers are done
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Planner placement (heist_plan_place): ticks and return with one more camera
 // ---------------------------------------------------------------------------
 //
@@ -5581,6 +5909,27 @@ hipError_t launch_plan_masked(const EnvParams& p, int horizon, double gamma, int
   }
   HEIST_MULTI_VARIANTS(HEIST_MASKED_CASE)
 #undef HEIST_MASKED_CASE
+  return hipErrorInvalidValue;  // not reached
+}
+
+// heist_plan_walls: heist_plan_masked's instances, LDS, support and grid of workgroups.
+hipError_t launch_plan_walls(const EnvParams& p, int horizon, double gamma, int M, int E, const int32_t* edits,
+                             const uint64_t* emitter_mask, uint8_t* valid_out, uint8_t* level_out, int16_t* ticks_out,
+                             double* value_out, int8_t* action_out, uint32_t* vis_out, int16_t* togo_cells_out,
+                             double* value_cells_out, hipStream_t st) {
+  if (!plan_value_variant_exists(p) || M < 1 || (size_t)p.n_envs * (size_t)M > 0x7fffffffull || E < 1 || E > 8)
+    return hipErrorInvalidValue;
+  const size_t lds = plan_value_lds(p);
+  const unsigned blocks = (unsigned)p.n_envs * (unsigned)M;
+#define HEIST_WALLS_CASE(W, D)                                                                                   \
+  if (p.multi_waves == W && p.vis_gap == D) {                                                                    \
+    hipLaunchKernelGGL((plan_walls_kernel<W, D>), dim3(blocks), dim3(64 * W), lds, st, p, horizon, gamma, M, E,  \
+                       edits, emitter_mask, valid_out, level_out, ticks_out, value_out, action_out, vis_out,     \
+                       togo_cells_out, value_cells_out);                                                         \
+    return hipGetLastError();                                                                                    \
+  }
+  HEIST_MULTI_VARIANTS(HEIST_WALLS_CASE)
+#undef HEIST_WALLS_CASE
   return hipErrorInvalidValue;  // not reached
 }
 

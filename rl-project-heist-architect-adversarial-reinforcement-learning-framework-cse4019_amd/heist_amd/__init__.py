@@ -8,10 +8,12 @@ __version__ = "0.1.0"
 
 from .environment import EnvironmentConfig, HeistEnvironment  # noqa: F401
 from .vec_env import (HeistEnv, LayoutBatch, PlanField, PlanMasked, PlanPlace, PlanPlay, PlanQ, PlanResult,  # noqa: F401
-                      PlanValue, STATUS_NAMES)
+                      PlanValue, PlanWalls, STATUS_NAMES)
 from .obs_compact import CompactObs, record_cells  # noqa: F401
 from .env_state import EnvState  # noqa: F401
 from .search import (ExpertData, GreedyAdversary, LookaheadResult, PlacementScan, PlanAblation, RelocationScan,  # noqa: F401
                      ablation_masks, architect_patrol, camera_candidates, exhaustive_lookahead, expert_data,
                      expert_labels, expert_rollout, follow_field, greedy_adversary, greedy_cameras, greedy_pick,
                      guard_candidates, guard_placement_scan, placement_scan, play_table, q_values, relocation_scan)
+from .search import (GreedyWalls, WallAblation, WallScan, greedy_walls, wall_ablation_edits,  # noqa: F401
+                     wall_candidates, wall_placement_scan)

@@ -41,6 +41,8 @@ SIGNATURES = {
     "heist_plan_value": (_i, [_vp, _i, _d, _vp, _vp, _vp, _vp, _vp, _vp]),
     "heist_plan_masked_supported": (_i, [_vp]),
     "heist_plan_masked": (_i, [_vp, _i, _d, _i] + [_vp] * 8),
+    "heist_plan_walls_supported": (_i, [_vp]),
+    "heist_plan_walls": (_i, [_vp, _i, _d, _i, _i] + [_vp] * 11),
     "heist_plan_place_supported": (_i, [_vp]),
     "heist_plan_place": (_i, [_vp, _i, _d, _i] + [_vp] * 10),
     "heist_plan_place_guard_supported": (_i, [_vp]),

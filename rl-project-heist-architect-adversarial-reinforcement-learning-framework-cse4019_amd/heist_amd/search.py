@@ -30,6 +30,11 @@ architect_patrol, guard_candidates, guard_placement_scan and greedy_adversary as
 guard with heist_plan_place_guard (HeistEnv.plan_place_guard): what one more Architect guard on any
 interior tile would cost the Solver, and the exact greedy adversary under the game's own cost table,
 cameras at 3 points against guards at 5.
+
+wall_ablation_edits, WallAblation, wall_candidates, wall_placement_scan and greedy_walls ask it of the
+third asset with heist_plan_walls (HeistEnv.plan_walls): which wall a layout's difficulty is due to,
+which one the Solver hides behind, what one more wall on any interior tile would do, and the exact
+greedy wall adversary, every variant cast against its own walls.
 """
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -1091,4 +1096,292 @@ def greedy_adversary(env, budget, camera_cands=None, guard_cands=None, horizon: 
         out.value.append(value)
         out.ticks.append(ticks)
         out.vis = base
+    return out
+
+
+# -- walls (heist_plan_walls, HeistEnv.plan_walls / plan_wall_ablate) -----------------------------
+
+_EMPTY, _WALL = 0, 1  # tile codes (utils.py)
+MAX_WALL_EDITS = 8    # heist_plan_walls: 1 <= E <= 8
+WALL_COST = 1         # the Architect's cost table (BUDGET_COSTS; heist_set_layout's purchase)
+
+
+def wall_ablation_edits(grid, max_walls: int):
+    """The leave-one-out wall edits of heist_plan_walls for grid [N, R, C] (a tensor or an array of any
+    integer type; HeistEnv.export()["grid"]), as (edits int32 [N, 1 + max_walls, 1, 3], filled bool
+    [N, max_walls]): variant 0 is the layout as built (op 0), variant 1 + j removes the env's j-th
+    interior WALL tile in row-major order (row, col, 2), and beyond the env's count -- filled False
+    -- the variant is op 0 again, equal to variant 0.  Walls past max_walls are left out.  The border
+    is not listed: it cannot be removed.  Pure torch, on the device of grid."""
+    grid = torch.as_tensor(grid)
+    if grid.dim() != 3 or grid.shape[1] < 3 or grid.shape[2] < 3:
+        raise ValueError("wall_ablation_edits: grid must be [N, R, C] with R, C >= 3")
+    k = int(max_walls)
+    if k < 0:
+        raise ValueError("wall_ablation_edits: max_walls must be >= 0")
+    n, R, C = (int(v) for v in grid.shape)
+    dev = grid.device
+    w = (grid[:, 1:-1, 1:-1] == _WALL).reshape(n, -1)                    # [N, cells], row-major
+    cells = int(w.shape[1])
+    order = torch.argsort((~w).to(torch.int8), dim=1, stable=True)       # the wall cells first, in order
+    if k > cells:
+        order = torch.cat([order, torch.zeros((n, k - cells), dtype=order.dtype, device=dev)], 1)
+    cell = order[:, :k]
+    filled = torch.arange(k, device=dev).reshape(1, k) < w.sum(1, keepdim=True)
+    z = torch.zeros_like(cell)
+    row = torch.where(filled, torch.div(cell, C - 2, rounding_mode="floor") + 1, z)
+    col = torch.where(filled, cell % (C - 2) + 1, z)
+    op = torch.where(filled, torch.full_like(cell, 2), z)
+    ed = torch.stack([row, col, op], -1).to(torch.int32)                 # [N, k, 3]
+    ed = torch.cat([torch.zeros((n, 1, 3), dtype=torch.int32, device=dev), ed], 1)
+    return ed.reshape(n, 1 + k, 1, 3).contiguous(), filled
+
+
+@dataclass
+class WallAblation:
+    """HeistEnv.plan_wall_ablate's output: what every interior wall of every layout does to the Solver,
+    from the leave-one-out variants of heist_plan_walls (variant 0: the layout as built; variant
+    1 + j: wall j removed; walls as in wall_ablation_edits).  PlanAblation's twin, with one more
+    flag: a wall stops rays as well as moves, so its removal can hurt.  Tensors on the tables' device:
+    ticks [N, 1 + K] int16, value [N, 1 + K] float64 -- PlanWalls.ticks / value;
+    filled [N, K] bool -- the env has a wall j;
+    ticks_saved [N, K] int16 -- ticks[:, :1] - ticks[:, 1:] where both are solvable, else 0 (negative
+        where the way without the wall is longer);
+    credit [N, K] float64 -- value[:, 1:] - value[:, :1], one subtraction, signed: what the wall costs
+        the Solver's optimal return; 0.0 where there is no wall j;
+    critical [N, K] bool -- the layout as built has no undetected way to the vault, the layout
+        without wall j has one;
+    redundant [N, K] bool -- a wall without which neither the ticks nor the value's bits change;
+    shielding [N, K] bool -- credit < 0: the Solver does worse without the wall."""
+    ticks: torch.Tensor
+    value: torch.Tensor
+    filled: torch.Tensor
+    ticks_saved: torch.Tensor
+    credit: torch.Tensor
+    critical: torch.Tensor
+    redundant: torch.Tensor
+    shielding: torch.Tensor
+
+    @staticmethod
+    def from_tables(ticks: torch.Tensor, value: torch.Tensor, filled: torch.Tensor) -> "WallAblation":
+        """The derived fields from the leave-one-out tables.  Pure torch."""
+        k = filled.shape[1]
+        if ticks.shape != (filled.shape[0], 1 + k) or value.shape != ticks.shape:
+            raise ValueError("WallAblation: ticks and value must be [N, 1 + K] for filled [N, K]")
+        filled = filled.bool()
+        t0, t1 = ticks[:, :1], ticks[:, 1:]
+        v0, v1 = value[:, :1].contiguous(), value[:, 1:].contiguous()
+        both = (t0 > 0) & (t1 > 0)
+        saved = torch.where(both, t0 - t1, torch.zeros_like(t1))
+        same = (t1 == t0) & (v1.view(torch.int64) == v0.view(torch.int64))
+        credit = torch.where(filled, v1 - v0, torch.zeros_like(v1))
+        return WallAblation(ticks, value, filled, saved, credit, filled & (t0 < 0) & (t1 > 0), filled & same,
+                            filled & (credit < 0))
+
+    def metrics(self) -> dict:
+        """The trainer's four figures for this batch (AdversarialTrainer(track_wall_credit=True)):
+        critical_wall_layout_frac -- the share of the unsolvable layouts that one wall's removal makes
+        solvable; redundant_wall_frac / shielding_wall_frac -- the share of the walls that are
+        redundant / shielding; wall_credit_mean -- the mean credit over the walls.  A share or a mean
+        over nothing is 0.0."""
+        f = self.filled
+        unsolv = self.ticks[:, 0] < 0
+        s = torch.stack([unsolv.sum().double(), (unsolv & self.critical.any(1)).sum().double(), f.sum().double(),
+                         self.redundant.sum().double(), self.shielding.sum().double(),
+                         torch.where(f, self.credit, torch.zeros_like(self.credit)).sum().double()]).cpu().tolist()
+        div = lambda a, b: a / b if b else 0.0  # noqa: E731
+        return {"critical_wall_layout_frac": div(s[1], s[0]), "redundant_wall_frac": div(s[3], s[2]),
+                "shielding_wall_frac": div(s[4], s[2]), "wall_credit_mean": div(s[5], s[2])}
+
+
+def wall_candidates(grid) -> torch.Tensor:
+    """One candidate wall per interior cell, for every env of grid [N, R, C], as heist_plan_walls'
+    edits int32 [N, M, 1, 3] = (row, col, 1), M = (R - 2)(C - 2), cells in row-major order:
+    candidate (r - 1)(C - 2) + c - 1 adds a wall on (r, c).  Every interior cell is listed whatever
+    stands on it -- the kernel's `valid` says which are EMPTY and free of the Solver -- so M and the
+    order are the same for every env.  Pure torch, on the device of grid."""
+    grid = torch.as_tensor(grid)
+    if grid.dim() != 3 or grid.shape[1] < 3 or grid.shape[2] < 3:
+        raise ValueError("wall_candidates: grid must be [N, R, C] with R, C >= 3")
+    n, R, C = (int(v) for v in grid.shape)
+    dev = grid.device
+    r = torch.arange(1, R - 1, dtype=torch.int32, device=dev).reshape(-1, 1).expand(R - 2, C - 2)
+    c = torch.arange(1, C - 1, dtype=torch.int32, device=dev).reshape(1, -1).expand(R - 2, C - 2)
+    rows = torch.stack([r, c, torch.ones_like(r)], -1)
+    return rows.reshape(1, -1, 1, 3).expand(n, -1, -1, -1).contiguous()
+
+
+@dataclass
+class WallScan:
+    """wall_placement_scan's output: what every candidate wall would do to every env, without the
+    visibility rows.  Tensors on the tables' device:
+    valid [N, M] bool, level [N, M] bool, ticks [N, M] int16, value [N, M] float64, action [N, M]
+    int8 -- PlanWalls's; ticks0 [N] int16, value0 [N] float64 -- the baseline: the envs as they
+    stand; cands [N, M, E, 3] int32 -- the candidates as given.
+    Unlike one more camera, one more wall can raise the Solver's value, open no way but close the
+    level, or cut the level off altogether: a wall that invalidates the level is not a buy (set_layout
+    would reject the layout), so only candidates with valid & level count below."""
+    valid: torch.Tensor
+    level: torch.Tensor
+    ticks: torch.Tensor
+    value: torch.Tensor
+    action: torch.Tensor
+    ticks0: torch.Tensor
+    value0: torch.Tensor
+    cands: Optional[torch.Tensor] = None
+
+    def eligible(self) -> torch.Tensor:
+        """[N, M] bool: the valid candidates that keep the level valid."""
+        return self.valid.bool() & self.level.bool()
+
+    def best(self) -> torch.Tensor:
+        """[N] int64: per env the eligible candidate of lowest Solver value, the lowest index on
+        ties, -1 where there is none."""
+        ok = self.eligible()
+        v = torch.where(ok, self.value, torch.full_like(self.value, float("inf")))
+        low = v.min(1, keepdim=True).values
+        m = self.value.shape[1]
+        idx = torch.arange(m, device=v.device, dtype=torch.int64).reshape(1, m).expand_as(v)
+        first = torch.where(ok & (v == low), idx, torch.full_like(idx, m)).min(1).values
+        return torch.where(first < m, first, torch.full_like(first, -1))
+
+    def headroom(self) -> torch.Tensor:
+        """[N] float64: value0 - value[best], one subtraction: the optimal return the best wall would
+        still take from the Solver; 0.0 where there is no best candidate, negative where even the
+        hardest wall helps."""
+        b = self.best()
+        vb = self.value.gather(1, b.clamp(min=0).reshape(-1, 1)).reshape(-1)
+        return torch.where(b >= 0, self.value0 - vb, torch.zeros_like(self.value0))
+
+    def _share(self, what: torch.Tensor, of: torch.Tensor) -> torch.Tensor:
+        a, b = (what & of).sum(1).double(), of.sum(1).double()
+        return torch.where(b > 0, a / b.clamp(min=1.0), torch.zeros_like(b))
+
+    def helps(self) -> torch.Tensor:
+        """[N] float64: per env the share of its eligible walls that raise the Solver's value (value >
+        value0); 0.0 for an env without an eligible wall."""
+        return self._share(self.value > self.value0.reshape(-1, 1), self.eligible())
+
+    def blocking(self) -> torch.Tensor:
+        """[N] float64: per env the share of its eligible walls that make a solvable layout unsolvable
+        (ticks0 >= 0, the variant's ticks < 0) while the level stays valid; 0.0 for an env whose
+        baseline is unsolvable or that has no eligible wall."""
+        return self._share((self.ticks < 0) & (self.ticks0 >= 0).reshape(-1, 1), self.eligible())
+
+    def invalidating(self) -> torch.Tensor:
+        """[N] float64: per env the share of its valid candidates that cut the start off from the
+        vault (level False); 0.0 for an env without a valid candidate."""
+        return self._share(~self.level.bool(), self.valid.bool())
+
+    def metrics(self) -> dict:
+        """wall_headroom_envs -- the envs that have a best candidate; wall_headroom_mean -- the mean
+        headroom over them; wall_helps_frac / wall_invalidating_frac -- the means of helps() /
+        invalidating() over the envs; wall_blocking_frac -- the mean of blocking() over the envs
+        whose baseline is solvable.  A mean over nothing is 0.0."""
+        has = self.best() >= 0
+        solv = self.ticks0 >= 0
+        z = torch.zeros_like(self.value0)
+        s = torch.stack([has.sum().double(), torch.where(has, self.headroom(), z).sum(), solv.sum().double(),
+                         torch.where(solv, self.blocking(), z).sum(), self.helps().sum(),
+                         self.invalidating().sum()]).cpu().tolist()
+        n = int(self.value0.shape[0])
+        div = lambda a, b: a / b if b else 0.0  # noqa: E731
+        return {"wall_headroom_mean": div(s[1], s[0]), "wall_blocking_frac": div(s[3], s[2]),
+                "wall_helps_frac": div(s[4], n), "wall_invalidating_frac": div(s[5], n),
+                "wall_headroom_envs": int(s[0])}
+
+
+def _plan_walls_chunked(env, ed, masks, H, gamma, max_bytes):
+    """HeistEnv.plan_walls over edits [N, M, E, 3] in chunks of M whose visibility rows stay under
+    max_bytes, the rows dropped: (valid, level, ticks, value, action), each [N, M]."""
+    from .obs_compact import record_words
+    per = 4 * max(H, 1) * env.n_envs * record_words(env.rows, env.cols)
+    step = max(1, int(max_bytes) // per)
+    parts = []
+    for m0 in range(0, int(ed.shape[1]), step):
+        mk = None if masks is None else masks[:, m0:m0 + step]
+        pw = env.plan_walls(ed[:, m0:m0 + step], masks=mk, horizon=H, gamma=gamma)
+        parts.append((pw.valid, pw.level, pw.ticks, pw.value, pw.action))
+        del pw
+    return tuple(torch.cat(x, 1) for x in zip(*parts))
+
+
+def wall_placement_scan(env, cands, horizon: Optional[int] = None, gamma: float = 1.0, masks=None,
+                        max_bytes: int = 1 << 30) -> WallScan:
+    """Every candidate of cands (int32 [N, M, E, 3] or [N, M, 3], wall_candidates' rows) tried on
+    every env of a HeistEnv as it stands: HeistEnv.plan_walls in chunks of M sized so that a chunk's
+    visibility rows (4 H N m W bytes) stay under max_bytes, the rows dropped, the tables
+    concatenated.  masks: plan_walls' emitter masks, int64 [N, M], or None.  The baseline ticks0 /
+    value0 is the variant without an edit and with every slot live.  Reads the envs only."""
+    H = min(int(env.config.max_steps), 1024) if horizon is None else int(horizon)
+    ed = torch.as_tensor(cands)
+    if ed.dim() == 3:
+        ed = ed.unsqueeze(2)
+    ed = ed.to(env.device)
+    if masks is not None:
+        masks = torch.as_tensor(masks).to(env.device)
+        if masks.dim() == 1:
+            masks = masks.reshape(1, -1).expand(env.n_envs, -1)
+    p0 = env.plan_walls(torch.zeros((env.n_envs, 1, 1, 3), dtype=torch.int32, device=env.device), horizon=H, gamma=gamma)
+    valid, level, ticks, value, action = _plan_walls_chunked(env, ed, masks, H, gamma, max_bytes)
+    return WallScan(valid, level, ticks, value, action, p0.ticks[:, 0], p0.value[:, 0], ed)
+
+
+@dataclass
+class GreedyWalls:
+    """greedy_walls' output, round by round (lists of [N] tensors): index -- the candidate each env
+    chose (-1: none); value / ticks -- the Solver's optimal value and fewest ticks with the walls
+    chosen so far; and edits int32 [N, rounds, 3] -- the walls as heist_plan_walls edits, (row, col,
+    1), or op 0 where the env chose none that round; value0 / ticks0 [N] -- the envs as they stand."""
+    index: list
+    value: list
+    ticks: list
+    edits: torch.Tensor
+    value0: torch.Tensor
+    ticks0: torch.Tensor
+
+
+def greedy_walls(env, n: int, cands=None, horizon: Optional[int] = None, gamma: float = 1.0,
+                 max_bytes: int = 1 << 30) -> GreedyWalls:
+    """The exact greedy wall adversary, without rebuilding a layout: n <= 8 rounds, round r planning
+    "the walls chosen so far + candidate" as an (r + 1)-edit variant of heist_plan_walls for every
+    candidate of cands (single edits int32 [N, M, 3] or [N, M, 1, 3]; None: wall_candidates of the
+    envs' grids).  A candidate is eligible when its variant is valid, keeps the level valid and
+    leaves an undetected way to the vault (valid & level & ticks >= 0) -- a tile chosen earlier
+    names one tile twice and is not valid; each env takes the eligible candidate with the largest
+    drop of the Solver's value, a drop above 0 only, the lowest index on ties.  Stops early when no
+    env chooses.  Reads the envs only."""
+    n = int(n)
+    if not 1 <= n <= MAX_WALL_EDITS:
+        raise ValueError("greedy_walls: need 1 <= n <= %d rounds (heist_plan_walls takes 8 edits)" % MAX_WALL_EDITS)
+    dev, N = env.device, env.n_envs
+    H = min(int(env.config.max_steps), 1024) if horizon is None else int(horizon)
+    cd = wall_candidates(env.grid_snapshot()) if cands is None else torch.as_tensor(cands)
+    cd = cd.to(dev).reshape(N, -1, 3).to(torch.int32)
+    M = int(cd.shape[1])
+    p0 = env.plan_walls(torch.zeros((N, 1, 1, 3), dtype=torch.int32, device=dev), horizon=H, gamma=gamma)
+    out = GreedyWalls([], [], [], torch.zeros((N, 0, 3), dtype=torch.int32, device=dev), p0.value[:, 0], p0.ticks[:, 0])
+    value, ticks = p0.value[:, 0].clone(), p0.ticks[:, 0].clone()
+    idx = torch.arange(M, device=dev, dtype=torch.int64).reshape(1, M)
+    for _ in range(n):
+        r = int(out.edits.shape[1])
+        ed = torch.cat([out.edits.reshape(N, 1, r, 3).expand(N, M, r, 3), cd.reshape(N, M, 1, 3)], 2).contiguous()
+        valid, level, tk, val, _ = _plan_walls_chunked(env, ed, None, H, gamma, max_bytes)
+        gain = value.reshape(-1, 1) - val
+        ok = valid & level & (tk >= 0) & (gain > 0)
+        g = torch.where(ok, gain, torch.full_like(gain, -1.0))
+        top = g.max(1, keepdim=True).values
+        first = torch.where(ok & (g == top), idx.expand_as(g), torch.full_like(idx.expand_as(g), M)).min(1).values
+        pick = torch.where(first < M, first, torch.full_like(first, -1))
+        if not bool((pick >= 0).any()):
+            break
+        i1 = pick.clamp(min=0).reshape(-1, 1)
+        chosen = cd.gather(1, i1.reshape(-1, 1, 1).expand(-1, 1, 3)).reshape(N, 3)
+        chosen = torch.where((pick >= 0).reshape(-1, 1), chosen, torch.zeros_like(chosen))
+        value = torch.where(pick >= 0, val.gather(1, i1).reshape(-1), value)
+        ticks = torch.where(pick >= 0, tk.gather(1, i1).reshape(-1), ticks)
+        out.edits = torch.cat([out.edits, chosen.reshape(N, 1, 3)], 1)
+        out.index.append(pick)
+        out.value.append(value.clone())
+        out.ticks.append(ticks.clone())
     return out

@@ -161,7 +161,7 @@ class AdversarialTrainer:  # training.py:115-790
                  solver_cadence: str = "rollout", obs_storage: str = "full", checkpoint_env: bool = False,
                  track_optimal: bool = False, track_optimal_return: bool = False,
                  track_emitter_credit: bool = False, track_camera_headroom: bool = False, headroom_envs: int = 64,
-                 headroom_headings: int = 8, track_guard_headroom: bool = False):
+                 headroom_headings: int = 8, track_guard_headroom: bool = False, track_wall_credit: bool = False):
         self.config = config or EnvironmentConfig()
         self.solver_episodes = solver_episodes_per_layout
         self.total_episodes = total_episodes
@@ -247,6 +247,16 @@ class AdversarialTrainer:  # training.py:115-790
         if self.track_guard_headroom and self.headroom_envs < 1:
             raise ValueError("track_guard_headroom needs headroom_envs >= 1")
         self._guard_headroom = None   # the three metrics of the latest scanned layout batch
+        # True: the same envs' interior walls are removed one at a time (HeistEnv.plan_wall_ablate at gamma 1, one
+        # launch on the side handle) and train_iteration reports critical_wall_layout_frac (the share of the
+        # unsolvable layouts that one wall's removal makes solvable), redundant_wall_frac (the share of the walls
+        # whose removal changes neither the fewest ticks nor the optimal return), shielding_wall_frac (the share
+        # the Solver does worse without) and wall_credit_mean (the mean signed optimal return a wall costs the
+        # Solver).  False: no launch, no metric, logs and checkpoints byte-identical
+        self.track_wall_credit = bool(track_wall_credit)
+        if self.track_wall_credit and self.headroom_envs < 1:
+            raise ValueError("track_wall_credit needs headroom_envs >= 1")
+        self._wall_credit = None      # the four metrics of the latest ablated layout batch
         if seed is not None:  # one stream per rank: ranks must not replay each other's layouts and actions
             torch.manual_seed(seed + dist_utils.rank())
             np.random.seed(seed + dist_utils.rank())
@@ -388,6 +398,8 @@ class AdversarialTrainer:  # training.py:115-790
                     self._headroom_layout_batch(good)
                 if self.track_guard_headroom:
                     self._guard_headroom_layout_batch(good)
+                if self.track_wall_credit:
+                    self._wall_credit_layout_batch(good)
             pending = bad if tries < 7 else np.zeros(0, np.int64)
             if len(bad) and tries >= 7:
                 self.b_valid[torch.as_tensor(bad, device=self.device)] = False
@@ -442,7 +454,7 @@ class AdversarialTrainer:  # training.py:115-790
         # env j of the side handle <- scanned env j mod len(ids): every env holds a layout, the first len(ids) count
         ok = side.load_state(self.env.save_state(ids), index=[j % len(ids) for j in range(k)])
         if not bool(ok.all()):
-            raise RuntimeError("track_camera_headroom / track_guard_headroom: the side handle rejected a saved env")
+            raise RuntimeError("track_camera_headroom / track_guard_headroom / track_wall_credit: the side handle rejected a saved env")
         return side, ids
 
     def _guard_headroom_layout_batch(self, env_ids):
@@ -454,6 +466,15 @@ class AdversarialTrainer:  # training.py:115-790
         m = len(ids)
         self._guard_headroom = PlacementScan(sc.valid[:m], sc.ticks[:m], sc.value[:m], sc.action[:m], sc.ticks0[:m],
                                              sc.value0[:m]).metrics("guard")
+
+    def _wall_credit_layout_batch(self, env_ids):
+        """The wall credit of the layouts just set on env_ids (fresh after reset): the first headroom_envs of
+        them, every interior wall removed in turn."""
+        from .search import WallAblation
+        side, ids = self._headroom_side(env_ids)
+        ab = side.plan_wall_ablate(gamma=1.0)
+        m = len(ids)
+        self._wall_credit = WallAblation.from_tables(ab.ticks[:m], ab.value[:m], ab.filled[:m]).metrics()
 
     def close(self):
         """Release the trainer's env handles: the batch's and, if a scan made one, the camera-headroom side
@@ -807,6 +828,8 @@ class AdversarialTrainer:  # training.py:115-790
             out.update(self._camera_headroom)
         if self.track_guard_headroom and self._guard_headroom is not None:
             out.update(self._guard_headroom)
+        if self.track_wall_credit and self._wall_credit is not None:
+            out.update(self._wall_credit)
         return out
 
     # -- supervised pre-training on exact labels (no reference counterpart) -------------------

@@ -249,6 +249,44 @@ class PlanPlace:
 
 
 @dataclass
+class PlanWalls:
+    """HeistEnv.plan_walls's output (heist_plan_walls, include/heist.h), device tensors; variant
+    (e, m) is env e with the tile edits edits[e, m] applied, under the emitter slots of masks[e, m]:
+    valid [N, M] bool -- every edit of the variant holds in the grid as it stands (an add on an
+        interior EMPTY tile that is not the Solver's cell, a remove of an interior WALL tile) and no
+        two name one tile; an invalid variant is planned with no edit at all (plan_masked's variant);
+    level [N, M] bool -- the variant's grid still joins the start tile to the vault over non-wall
+        tiles (heist_bfs_valid's answer; set_layout would reject the level where it is False);
+    ticks [N, M] int16 -- the fewest ticks to a clean vault arrival from the Solver's cell (-1: none);
+    value [N, M] float64, action [N, M] int8 -- the largest discounted return from there and the
+        lowest action that starts it (PlanValue's at that cell);
+    vis [H, N, M, W] int32 -- row k - 1: the variant's visibility plane of the k-th tick from now,
+        4 H N M W bytes;
+    togo [N, M, R, C] int16, value_cells [N, M, R, C] float64 or None -- the whole tables
+        (PlanField.togo / PlanValue.value of the variant; an added wall cell holds -1 / 0.0); with
+        cells=True only;
+    edits [N, M, E, 3] int32 -- the edits as given: (row, col, op), op 0 none, 1 add, 2 remove;
+    masks [N, M] int64 or None -- the emitter masks as given (None: every slot live);
+    tick [N] int32 -- each env's tick at the call, -1 where it was done (PlanValue.tick)."""
+    valid: torch.Tensor
+    level: torch.Tensor
+    ticks: torch.Tensor
+    value: torch.Tensor
+    action: torch.Tensor
+    vis: torch.Tensor
+    togo: Optional[torch.Tensor]
+    value_cells: Optional[torch.Tensor]
+    edits: torch.Tensor
+    masks: Optional[torch.Tensor]
+    tick: torch.Tensor
+    rows: int
+    cols: int
+    gamma: float = 1.0
+
+    vis_mask = PlanMasked.vis_mask
+
+
+@dataclass
 class PlanQ:
     """HeistEnv.plan_q's output (heist_plan_q, include/heist.h; heist_amd.search.q_values gives the
     same on any device): the exact action values of visited states, [K, N] time-major, state
@@ -666,6 +704,81 @@ class HeistEnv:
         j = torch.arange(mc + mg, device=self.device).reshape(1, -1)
         filled = torch.where(j < mc, j < ex["n_cams"].reshape(-1, 1), j - mc < ex["n_guards"].reshape(-1, 1))
         return PlanAblation.from_tables(pm.ticks, pm.value, filled)
+
+    # -- planner walls (heist_plan_walls) ------------------------------------------------------
+    @property
+    def plan_walls_supported(self) -> int:
+        """heist_plan_walls_supported: 1 when plan_walls() has a kernel for this handle (where
+        plan_masked() has one: every grid up to 32 x 32; 0 at 64 x 64)."""
+        with torch.cuda.device(self.device):
+            d = int(nat.lib().heist_plan_walls_supported(self._h))
+        nat.check(0 if d >= 0 else d, "heist_plan_walls_supported")
+        return d
+
+    def plan_walls(self, edits, masks=None, horizon: Optional[int] = None, gamma: float = 1.0,
+                   cells: bool = False) -> "PlanWalls":
+        """heist_plan_walls: every env as it stands planned with walls added or removed, M variants
+        per env in one launch that casts every live emitter against the variant's own walls -- the
+        fewest ticks to the vault and the largest discounted return from the Solver's cell on the
+        edited grid, whether the edits hold, whether the level is still valid, plus every variant's
+        visibility planes and, with cells, the whole tables.  edits: int32 [N, M, E, 3] with
+        1 <= E <= 8, or [N, M, 3] for E = 1, each edit (row, col, op): op 0 none, 1 add a wall,
+        2 remove one.  masks: plan_masked's int64 [N, M] or [M], or None for every slot live.
+        horizon and gamma as in plan_value.  vis takes 4 H N M W bytes.  Reads the envs only."""
+        from .obs_compact import record_words
+        H = min(int(self.config.max_steps), 1024) if horizon is None else int(horizon)
+        n, R, C, h = self.n_envs, self.rows, self.cols, max(H, 0)
+        ed = torch.as_tensor(edits)
+        if ed.dtype != torch.int32 or ed.dim() not in (3, 4) or ed.shape[0] != n or ed.shape[-1] != 3:
+            raise ValueError("plan_walls: edits must be an int32 [%d, M, E, 3] or [%d, M, 3] tensor" % (n, n))
+        if ed.dim() == 3:
+            ed = ed.unsqueeze(2)
+        ed = ed.to(self.device).contiguous()
+        M, E = int(ed.shape[1]), int(ed.shape[2])
+        mk = None
+        if masks is not None:
+            mk = torch.as_tensor(masks)
+            if mk.dtype != torch.int64 or mk.dim() not in (1, 2) or (mk.dim() == 2 and mk.shape[0] != n):
+                raise ValueError("plan_walls: masks must be an int64 [%d, M] or [M] tensor" % n)
+            if mk.dim() == 1:
+                mk = mk.reshape(1, -1).expand(n, -1)
+            if int(mk.shape[1]) != M:
+                raise ValueError("plan_walls: masks must hold one mask per variant (M = %d)" % M)
+            mk = mk.to(self.device).contiguous()
+        kw = dict(device=self.device)
+        valid = torch.empty((n, M), dtype=torch.uint8, **kw)
+        level = torch.empty((n, M), dtype=torch.uint8, **kw)
+        ticks = torch.empty((n, M), dtype=torch.int16, **kw)
+        value = torch.empty((n, M), dtype=torch.float64, **kw)
+        action = torch.empty((n, M), dtype=torch.int8, **kw)
+        vis = torch.empty((h, n, M, record_words(R, C)), dtype=torch.int32, **kw)
+        tcells = torch.empty((n, M, R, C), dtype=torch.int16, **kw) if cells else None
+        vcells = torch.empty((n, M, R, C), dtype=torch.float64, **kw) if cells else None
+        with torch.cuda.device(self.device):
+            nat.check(nat.lib().heist_plan_walls(self._h, H, float(gamma), M, E, nat.ptr(ed) if M and E else None,
+                                                 nat.ptr(mk), nat.ptr(valid), nat.ptr(level), nat.ptr(ticks),
+                                                 nat.ptr(value), nat.ptr(action), nat.ptr(vis), nat.ptr(tcells),
+                                                 nat.ptr(vcells), self._stream()), "heist_plan_walls")
+        ex = self.export()
+        tick = torch.where(ex["done"] != 0, torch.full_like(ex["tick"], -1), ex["tick"])
+        return PlanWalls(valid.view(torch.bool), level.view(torch.bool), ticks, value, action, vis, tcells, vcells, ed,
+                         mk, tick, R, C, float(gamma))
+
+    def plan_wall_ablate(self, max_walls: Optional[int] = None, horizon: Optional[int] = None, gamma: float = 1.0):
+        """Every env's interior walls removed one at a time: plan_walls with
+        heist_amd.search.wall_ablation_edits of the envs' own grids, as a
+        heist_amd.search.WallAblation -- ticks and value of the layout as built (column 0) and
+        without wall j in row-major order (column 1 + j), each wall's signed credit, and which walls
+        are critical, redundant or shielding.  max_walls: the columns (None: the largest count of
+        the batch).  One launch; reads the envs only."""
+        from .search import WallAblation, wall_ablation_edits
+        grid = self.grid_snapshot()
+        if max_walls is None:
+            g = grid[:, 1:-1, 1:-1]
+            max_walls = int((g == 1).reshape(g.shape[0], -1).sum(1).max().item()) if g.numel() else 0
+        ed, filled = wall_ablation_edits(grid, int(max_walls))
+        pw = self.plan_walls(ed, horizon=horizon, gamma=gamma)
+        return WallAblation.from_tables(pw.ticks, pw.value, filled.to(self.device))
 
     # -- planner placement (heist_plan_place) --------------------------------------------------
     @property

@@ -51,6 +51,12 @@ existing launch that casts the same rays, same process, same handle, HIP events.
                                                  # cameras and to the twin-handle route, then a full guard scan of 64
                                                  # envs with headroom per budget point next to the best camera's; also
                                                  # written to profiles/plan_place_guard.log
+  python tools/plan_env.py --walls [--gamma G]   # the planner walls (heist_plan_walls, HeistEnv.plan_walls) on the
+                                                 # Architect batch: 8 wall adds per env next to the same launch without
+                                                 # edits, to heist_plan_masked on a handle without the guard cone cache
+                                                 # and to the twin-handle route, then a full wall_placement_scan of 64
+                                                 # envs and the wall ablation of the batch; also written to
+                                                 # profiles/plan_walls.log
 
 The planner only reads the envs, so every timed launch does the same work from the same state
 (fresh after reset): `--warmup` untimed launches, then `--runs` launches each between two events;
@@ -663,6 +669,133 @@ def place_guard_mode(args, dev):
         fh.write("\n".join(lines) + "\n")
 
 
+def walls_mode(args, dev):
+    """heist_plan_walls on the Architect batch, one JSON line per row, each with its N, M and device
+    seconds per variant: (a) the launch at M = 8 with one random valid add per variant; (a') the same
+    launch with op 0 everywhere; (b) heist_plan_masked with every slot on, on a handle of the same
+    layouts that caches no guard cone -- the same work without edits; (c) the route without the
+    kernel -- variant 0 of every env laid into a twin handle by set_layout_batch + reset + plan_field
+    + plan_value -- with the bitwise-equality flag; (d) a full wall_placement_scan of 64 envs x every
+    interior tile, with the best wall's headroom per budget point; (e) the wall ablation of every
+    layout, with the shares of critical, redundant and shielding walls."""
+    from heist_amd.search import WALL_COST, wall_candidates, wall_placement_scan
+    from heist_amd.vec_env import LayoutBatch
+    H = min(args.horizon or args.max_steps, 1024)
+    N, R, M = args.envs, args.grid, 8
+    env = make_env(args, "architect", dev)
+    kc = env.kernel_config()
+    assert env.plan_walls_supported == 1, kc
+    head = {"config": "%dx%d" % (R, R), "layouts": "architect", "horizon": H, "gamma": args.gamma,
+            "multi_waves": kc["multi_waves"], "guard_cones": kc["guard_cones"]}
+    lines = []
+
+    def emit(row):
+        lines.append(json.dumps(dict(head, **row)))
+        print(lines[-1], flush=True)
+
+    def med(fn, runs=None):
+        ms = timed(dev, fn, args.warmup, runs or args.runs)
+        return statistics.median(ms), ms
+
+    # (a) one random valid add per variant: M = 8 of the env's interior EMPTY tiles (the start holds the Solver)
+    gen = torch.Generator().manual_seed(args.seed)
+    grid = env.grid_snapshot().cpu()
+    free = (grid[:, 1:-1, 1:-1] == 0).reshape(N, -1)
+    score = torch.rand(free.shape, generator=gen) + free.double()          # the EMPTY tiles first, in random order
+    cell = score.argsort(1, descending=True)[:, :M]
+    assert bool(free.gather(1, cell).all()), "an env with fewer than 8 EMPTY tiles"
+    ed = torch.stack([cell // (R - 2) + 1, cell % (R - 2) + 1, torch.ones_like(cell)], -1).to(torch.int32)
+    ed = ed.reshape(N, M, 1, 3).to(dev)
+    pw = env.plan_walls(ed, horizon=H, gamma=args.gamma)
+    valid, level, ticks_a, value_a = pw.valid.clone(), pw.level.clone(), pw.ticks.clone(), pw.value.clone()
+    del pw
+    a, a_ms = med(lambda: env.plan_walls(ed, horizon=H, gamma=args.gamma))
+    emit({"row": "a", "what": "plan_walls, one random valid add per variant", "envs": N, "M": M,
+          "valid_frac": float(valid.float().mean()), "level_frac": float(level.float().mean()),
+          "launch_ms_median": a, "launch_ms": a_ms, "seconds_per_variant": a * 1e-3 / (N * M)})
+    none = torch.zeros_like(ed)
+    p0 = env.plan_walls(none, horizon=H, gamma=args.gamma)
+    ticks_0, value_0, vis_0 = p0.ticks.clone(), p0.value.clone(), p0.vis[:, :, 0].clone()
+    del p0
+    z, z_ms = med(lambda: env.plan_walls(none, horizon=H, gamma=args.gamma))
+    emit({"row": "a'", "what": "plan_walls, op 0 everywhere", "envs": N, "M": M, "launch_ms_median": z, "launch_ms": z_ms,
+          "seconds_per_variant": z * 1e-3 / (N * M), "edits_over_none": a / z})
+
+    # (b) plan_masked, every slot on, on a handle of the same layouts without the guard cone cache
+    layouts, spent = env.layout_lists()
+    plain = HeistEnv(N, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                     auto_reset=True)
+    plain.set_guard_cones(False)
+    plain.set_layout_batch(LayoutBatch.from_lists(layouts, spent, plain.max_cams, plain.max_guards, plain.max_path, dev, R, R))
+    plain.reset()
+    on = torch.full((N, M), -1, dtype=torch.int64, device=dev)
+    pm = plain.plan_masked(on, H, gamma=args.gamma)
+    same_b = bool(torch.equal(pm.ticks, ticks_0) and torch.equal(pm.value.view(torch.int64), value_0.view(torch.int64))
+                  and torch.equal(pm.vis[:, :, 0], vis_0))
+    del pm, vis_0
+    b, b_ms = med(lambda: plain.plan_masked(on, H, gamma=args.gamma))
+    emit({"row": "b", "what": "plan_masked, every slot on, guard cones off", "envs": N, "M": M,
+          "guard_cones": plain.kernel_config()["guard_cones"], "equals_plan_walls_without_edits_bitwise": same_b,
+          "launch_ms_median": b, "launch_ms": b_ms, "seconds_per_variant": b * 1e-3 / (N * M), "walls_over_masked": a / b})
+    plain.close()
+
+    # (c) the route without the kernel: variant 0 of every env as one more wall of a twin's layout
+    plus = [(list(w) + [(int(rc[0]), int(rc[1]))], cams, g) for (w, cams, g), rc in zip(layouts, ed[:, 0, 0, :2].tolist())]
+    twin = HeistEnv(N, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                    auto_reset=True)
+    lb = LayoutBatch.from_lists(plus, [sp + WALL_COST for sp in spent], twin.max_cams, twin.max_guards, twin.max_path,
+                                dev, R, R)
+    sr, sc = env.config.start_pos
+
+    def route():
+        twin.set_layout_batch(lb)
+        twin.reset()
+        return twin.plan_field(H), twin.plan_value(H, gamma=args.gamma)
+
+    pf, pv = route()
+    v0 = valid[:, 0] & level[:, 0]
+    same = bool(torch.equal(pf.togo[:, sr, sc][v0], ticks_a[:, 0][v0])
+                and torch.equal(pv.value[:, sr, sc][v0].contiguous().view(torch.int64),
+                                value_a[:, 0][v0].contiguous().view(torch.int64)))
+    del pf, pv
+    c, c_ms = med(route)
+    emit({"row": "c", "what": "set_layout_batch + reset + plan_field + plan_value on a twin handle", "envs": N, "M": 1,
+          "twin_equals_plan_walls_bitwise_on_valid_level_variants": same, "pass_ms_median": c, "pass_ms": c_ms,
+          "seconds_per_variant": c * 1e-3 / N, "route_over_walls": (c / N) / (a / (N * M))})
+    twin.close()
+
+    # (d) a full scan: 64 envs, a wall on every interior tile
+    n = min(64, N)
+    side = HeistEnv(n, env.config, max_cams=env.max_cams, max_guards=env.max_guards, max_path=env.max_path, device=dev,
+                    auto_reset=True)
+    assert bool(side.load_state(env.save_state(list(range(n)))).all())
+    full = wall_candidates(side.grid_snapshot())
+    scan = wall_placement_scan(side, full, H, gamma=args.gamma)
+    d, d_ms = med(lambda: wall_placement_scan(side, full, H, gamma=args.gamma), runs=min(args.runs, 3))
+    Mf = int(full.shape[1])
+    wm = scan.metrics()
+    emit({"row": "d", "what": "wall_placement_scan, every interior tile", "envs": n, "M": Mf, "scan_ms_median": d,
+          "scan_ms": d_ms, "seconds_per_variant": d * 1e-3 / (n * Mf), "valid_frac": float(scan.valid.float().mean()),
+          "solvable_baselines": int((scan.ticks0 >= 0).sum()), **wm, "headroom_max": float(scan.headroom().max()),
+          "wall_headroom_per_point": wm["wall_headroom_mean"] / WALL_COST})
+    side.close()
+
+    # (e) the wall ablation of every layout: one launch, M = 1 + the batch's largest wall count
+    ab = env.plan_wall_ablate(horizon=H, gamma=args.gamma)
+    Me = int(ab.ticks.shape[1])
+    e, e_ms = med(lambda: env.plan_wall_ablate(horizon=H, gamma=args.gamma), runs=min(args.runs, 3))
+    emit({"row": "e", "what": "wall ablation (plan_wall_ablate)", "envs": N, "M": Me, "walls": int(ab.filled.sum()),
+          "pass_ms_median": e, "pass_ms": e_ms, "seconds_per_variant": e * 1e-3 / (N * Me),
+          "unsolvable_layouts": int((ab.ticks[:, 0] < 0).sum()), **ab.metrics(),
+          "credit_min": float(ab.credit.min()), "credit_max": float(ab.credit.max())})
+    env.close()
+    out_path = args.out if args.out != DEFAULT_OUT else os.path.join(ROOT, "profiles", "plan_walls.log")
+    os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+    with open(out_path, "w") as fh:
+        fh.write("$ python tools/plan_env.py --walls --gamma %r\n" % args.gamma)
+        fh.write("\n".join(lines) + "\n")
+
+
 DEFAULT_OUT = os.path.join(ROOT, "profiles", "plan_field.log")
 
 
@@ -696,12 +829,17 @@ def main(argv=None):
     ap.add_argument("--place-guard", action="store_true", help="time heist_plan_place_guard next to heist_plan_place "
                     "and to the twin-handle route on the Architect batch, then a full guard_placement_scan of 64 envs "
                     "(log: profiles/plan_place_guard.log)")
+    ap.add_argument("--walls", action="store_true", help="time heist_plan_walls next to heist_plan_masked without the "
+                    "guard cone cache and to the twin-handle route on the Architect batch, then a full wall_placement_scan "
+                    "of 64 envs and the wall ablation of the batch (log: profiles/plan_walls.log)")
     ap.add_argument("--out", default=DEFAULT_OUT, help="--field's log (--value's: profiles/plan_value.log, --play's: "
                     "profiles/plan_play.log, --q's: profiles/plan_q.log, --ablate's: profiles/plan_masked.log, --place's: "
                     "profiles/plan_place.log)")
     args = ap.parse_args(argv)
     dev = torch.device("cuda:0")
     torch.cuda.set_device(dev)
+    if args.walls:
+        return walls_mode(args, dev)
     if args.place_guard:
         return place_guard_mode(args, dev)
     if args.place:

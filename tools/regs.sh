@@ -3,7 +3,8 @@
 # the planner kernels' LDS is dynamic -- plan_lds / plan_value_lds in heist_env.hip -- so their LDS Size prints 0).
 # usage: tools/regs.sh [regex]   (default: step|reset|cones; `plan` the planner's and the planner
 #        field's instances, `field` plan_field_kernel's alone, `value` plan_value_kernel's alone,
-#        `masked` plan_masked_kernel's alone, `place` plan_place_kernel's and plan_place_guard_kernel's)
+#        `masked` plan_masked_kernel's alone, `place` plan_place_kernel's and plan_place_guard_kernel's,
+#        `walls` plan_walls_kernel's alone)
 #        tools/regs.sh play      plan_play_kernel (heist_play.hip), with its SGPRs and LDS
 #        tools/regs.sh q         plan_q_kernel (heist_q.hip), the same columns
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
